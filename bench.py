@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the disparity hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--algo fast|exact] [--frames 16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--algo fast|exact] [--frames 16] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -62,7 +62,14 @@ def parse_args():
     ap.add_argument("--no-parity-probe", action="store_true",
                     help="skip the untimed 1-frame parity probe (the profiling scripts do: its launches would be averaged "
                          "into the per-kernel statistics)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline region's last step returned as DIR/<name>.npy "
+                         "(float32, at most 60 MiB in all; larger arrays as a fixed, seeded sample, see dump_outputs); "
+                         "rank 0's frames")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def check_gpu_count(n_ranks, backend, n_devices):
@@ -240,14 +247,58 @@ def exact_lcn_pipeline_probe(te, frames, idx, pat_lcn):
 
 
 def lcn_and_match(te, frames, pat_lcn, n_disp, lcn_algo, prepared, return_volume=True):
-    """LCN + NCC volume + argmax of one batch the way --lcn-algo says; returns (lcn, idx, best, volume | None)."""
+    """LCN + NCC volume + argmax of one batch the way --lcn-algo says; returns what the caller receives, by name:
+    lcn, lcn_std, disparity_index, best_score and cost_volume (None without return_volume)."""
     if lcn_algo.startswith("fused"):
         out = te.lcn_xcorrvol_argmax(frames, pat_lcn, n_disp, BS, LCN_RADIUS, LCN_EPS, return_volume=return_volume,
                                      lcn_algo="exact" if lcn_algo == "fused_exact" else "fast", prepared=prepared)
-        return (out[0], out[2], out[3], out[4] if return_volume else None)
-    x, _ = te.lcn(frames, LCN_RADIUS, LCN_EPS, algo=lcn_algo)
-    out = te.xcorrvol_argmax(x, pat_lcn, n_disp, BS, return_volume=return_volume, prepared=prepared)
-    return (x, out[0], out[1], out[2] if return_volume else None)
+        x, std, idx, best = out[:4]
+        vol = out[4] if return_volume else None
+    else:
+        x, std = te.lcn(frames, LCN_RADIUS, LCN_EPS, algo=lcn_algo)
+        out = te.xcorrvol_argmax(x, pat_lcn, n_disp, BS, return_volume=return_volume, prepared=prepared)
+        idx, best = out[:2]
+        vol = out[2] if return_volume else None
+    return {"lcn": x, "lcn_std": std, "disparity_index": idx, "best_score": best, "cost_volume": vol}
+
+
+DUMP_BYTES = 60 << 20                      # --dump-outputs: under 64 MB in all
+DUMP_MIN_SAMPLE = 1 << 20                  # elements kept back for every array still to come
+DUMP_SEED = 20240611
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: write each (name, tensor) of `arrays` as outdir/<name>.npy, float32 (float64 stays float64;
+    integer indices are exact in float32).  Smallest first, an array is written whole while it fits the budget
+    left after DUMP_MIN_SAMPLE elements kept back for each array still to come; the arrays that do not share what
+    remains as fixed samples: the flat (C-order) elements at the sorted indices
+    np.random.RandomState(DUMP_SEED).randint(0, numel, k), the same in every run of the same shape.
+    Returns name -> {"shape", "written", "sampled"} for the JSON line."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(((n, t.detach()) for n, t in arrays if t is not None), key=lambda item: item[1].numel())
+    size = [8 if t.dtype == torch.float64 else 4 for _, t in items]
+    whole, left = [], DUMP_BYTES
+    for i, (_, t) in enumerate(items):
+        keep = DUMP_MIN_SAMPLE * sum(size[i + 1:])
+        fits = t.numel() * size[i] <= left - keep
+        whole.append(fits)
+        if fits:
+            left -= t.numel() * size[i]
+    n_sampled = sum(size[i] for i in range(len(items)) if not whole[i])
+    per = left // n_sampled if n_sampled else 0            # elements per sampled array
+    manifest = {}
+    for i, (name, t) in enumerate(items):
+        t = t if t.dtype == torch.float64 else t.float()
+        if whole[i] or per >= t.numel():
+            a = t.contiguous().cpu().numpy()
+        else:
+            ix = np.sort(np.random.RandomState(DUMP_SEED).randint(0, t.numel(), size=per, dtype=np.int64))
+            a = torch.take(t, torch.from_numpy(ix).to(t.device)).cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        manifest[name] = {"shape": list(t.shape), "written": int(a.size), "sampled": int(a.size) < t.numel()}
+    return manifest
 
 
 def also_measured(te, L, frames, pat_lcn, args):
@@ -311,9 +362,9 @@ def run_config4(args):
     prepared = te.prepare_pattern(pat_lcn, frames_n, D4, BS)     # the pattern half of the matcher's pre-pass, once per run
 
     def step():
-        x, idx, best, vol = lcn_and_match(te, fr, pat_lcn, D4, args.lcn_algo, prepared)
-        cen = te.costvol(x[:, 0], pat_lcn[0], D4, BS, "census_sad", 0.5, algo="fast")
-        return x, idx, vol, cen
+        out = lcn_and_match(te, fr, pat_lcn, D4, args.lcn_algo, prepared)
+        out["census_cost_volume"] = te.costvol(out["lcn"][:, 0], pat_lcn[0], D4, BS, "census_sad", 0.5, algo="fast")
+        return out
 
     import gc
     gc.collect()
@@ -339,7 +390,8 @@ def run_config4(args):
     L.ctd_kernel_timing_enable(0)
     avg_ms, cols = ctypes.c_double(0), ctypes.c_int(0)
     n_launch = L.ctd_kernel_timing_collect(ctypes.byref(avg_ms), ctypes.byref(cols))
-    x = held[0]
+    dumped = dump_outputs(args.dump_outputs, list(held.items())) if args.dump_outputs else None
+    x = held["lcn"]
     # the census kernel alone, device time (our kernels launch on torch's current stream, so torch events bracket them)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(10):
@@ -397,7 +449,7 @@ def run_config4(args):
         fr2 = torch.cat([fr, torch.from_numpy(workloads.uniform_frame(4321, H4, W4)).to(device).reshape(1, 1, H4, W4)])
         x2, _ = te.lcn(fr2, LCN_RADIUS, LCN_EPS, algo="exact" if args.lcn_algo in ("exact", "fused_exact") else "fast")
         prep2 = te.prepare_pattern(pat_lcn, 2, D4, BS)
-        idx_timed = held[1][:1].clone()                  # (the one-frame step's volumes make room for the two-frame call's)
+        idx_timed = held["disparity_index"][:1].clone()  # (the one-frame step's volumes make room for the two-frame call's)
         del held
         L.ctd_kernel_timing_enable(2 * args.steps + 64)
         for _ in range(20):
@@ -414,14 +466,16 @@ def run_config4(args):
         out["ncc_two_frames_per_call"] = {"avg_launch_ms": ms2.value, "launches": n2, "achieved_GBs": ach2,
                                           "frac_of_hbm_peak": ach2 / HBM_PEAK_GBS if ach2 else None}
         del h2, x2, prep2, fr2
-        held = (x, idx_timed)
+        held = {"lcn": x, "disparity_index": idx_timed}
     # indices of the timed step's frame 0 against the reference-order kernel on the same LCN'd frame (first index on ties)
     ref_vol = te.xcorrvol_batch(x[:1].contiguous(), pat_lcn, D4, BS, algo="exact")
     ref_idx, _ = te.argmax_disp(ref_vol)
-    out["disparity_mae_vs_ref"] = float((held[1][:1].to(torch.int64) - ref_idx).abs().to(torch.float64).mean().item())
+    out["disparity_mae_vs_ref"] = float((held["disparity_index"][:1].to(torch.int64) - ref_idx).abs().to(torch.float64).mean().item())
     del ref_vol
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_config4(pat_lcn.cpu(), x[0].cpu(), H4, W4, D4)
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     emit(json.dumps(out))
 
 
@@ -554,14 +608,13 @@ def main():
 
     def step2():
         """config 2: LCN -> NCC volume (materialised) -> argmax with reference indices"""
-        x, idx, best, vol = lcn_and_match(te, frames, pat_lcn, D, args.lcn_algo, prepared)
-        return x, idx, vol
+        return lcn_and_match(te, frames, pat_lcn, D, args.lcn_algo, prepared)
 
     def step3(exchange=True):
         """config 3: the same, then disparity -> depth (+1: disparity 0 would be depth 1e12), the symmetric geometric loss
         of the frame pairs (i, i + frames/2) and the path's only exchange: every rank's loss scalar to every rank"""
-        x, idx, best, vol = lcn_and_match(te, frames, pat_lcn, D, args.lcn_algo, prepared)
-        depth = te.idx_to_depth(idx, FOCAL * BASELINE_M, 1.0).view(-1, 1, H, W)
+        out = lcn_and_match(te, frames, pat_lcn, D, args.lcn_algo, prepared)
+        depth = te.idx_to_depth(out["disparity_index"], FOCAL * BASELINE_M, 1.0).view(-1, 1, H, W)
         loss = geo(depth[:half], depth[half:2 * half], Ra, ta, Rb, tb)
         if exchange:
             k = n_exchanged[0] % len(ring)
@@ -572,7 +625,8 @@ def main():
                                                       force=args.force_dist)
             ring[k] = (buf, work, src)
             n_exchanged[0] += 1
-        return x, idx, vol
+        out["geometric_loss"] = loss
+        return out
 
     def barrier():
         torch.cuda.synchronize()
@@ -636,8 +690,10 @@ def main():
     for _ in range(100):
         t_s = time.perf_counter()
         for _ in range(10):
-            held = head()                         # outputs held like in the timed loop: the caching allocator ends up
-                                                  # owning both sets of output buffers that loop alternates between
+            spare, held = held, head()            # outputs held like in the timed loop, plus the set this function
+                                                  # holds while it runs that loop: the caching allocator ends up owning
+                                                  # all three sets, so no timed step allocates (with --warmup 1 the first
+                                                  # timed step used to; a 4-step region once came out at 13 ms per step)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t_s
         L.ctd_kernel_timing_collect(None, None)
@@ -646,8 +702,11 @@ def main():
         if prev is not None and abs(dt - prev) <= 0.03 * min(dt, prev) and time.perf_counter() - t_settle >= 0.25:
             break
         prev = dt
+    spare = None
     # ---- headline region: config 2 (config 3 when --workload config3 asks for that region alone)
-    elapsed, avg_launch_ms, n_launch, cols, (x, idx, vol) = timed_region(head if want2 else step3)
+    elapsed, avg_launch_ms, n_launch, cols, head_out = timed_region(head if want2 else step3)
+    held = None                                   # from here on head_out is the one set held between regions
+    x, idx = head_out["lcn"], head_out["disparity_index"]
     # run-to-run spread: two more regions of the same K steps (reported next to the headline one, never instead of it)
     repeats = []
     if not args.headline_only:
@@ -658,11 +717,14 @@ def main():
     if want2 and want3:
         for _ in range(10):
             step3(exchange=False)                 # the geometric kernels' first launches (code objects, workspaces): untimed
-        c3_elapsed, _, _, _, _ = timed_region(step3)
+        c3_elapsed, _, _, _, c3_out = timed_region(step3)
         c3 = max_over_ranks(c3_elapsed)
+        head_out["config3_geometric_loss"] = c3_out["geometric_loss"]
+        del c3_out
     gc.enable()
     L.ctd_kernel_timing_enable(0)
     L.ctd_kernel_timing_collect(None, None)
+    dumped = dump_outputs(args.dump_outputs, list(head_out.items())) if args.dump_outputs and rank == 0 else None
     elapsed = max_over_ranks(elapsed)
     ranks_seen = dist.get_world_size() if dist is not None else 1
 
@@ -790,6 +852,8 @@ def main():
             out["also_measured"] = also_measured(te, L, frames, pat_lcn, args)
         if not args.no_cpu_baseline and dist is None:          # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(pat_lcn.cpu(), x[:min(args.frames, 32)].cpu())
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         emit(json.dumps(out))
     if dist is not None:
         for slot in ring:                                          # no exchange left in flight at tear-down

@@ -24,8 +24,8 @@ def run_bench(*flags, env=None):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line():
-    j = run_bench("--steps", "4", "--warmup", "1", "--no-cpu-baseline")
+def test_single_gpu_line(tmp_path):
+    j = run_bench("--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
     assert j["n_gpus"] == 1 and j["steps"] == 4 and j["warmup"] == 1 and j["higher_is_better"] is True
     assert j["unit"] == "Mpix*disp/s" and j["dtype"] == "f32" and j["data"] == "synthetic" and j["scaling"] == "weak"
     assert j["vs_baseline"] is None and j["disparity_mae_vs_ref"] == 0.0
@@ -49,6 +49,17 @@ def test_single_gpu_line():
     # end-to-end index parity of the timed step from the raw frame through the exact LCN: reported, near-ties only
     e2e = j["disparity_mae_detail"]["timed_workload_frame0_vs_exact_lcn_pipeline"]
     assert e2e["pixels"] == 432 * 512 and e2e["pixels_differing"] <= 8 and "scaling_note" not in cfg
+    # --dump-outputs: the timed step's outputs, float32, under 64 MB; indices, scores and LCN whole, the volume sampled
+    import numpy as np
+    d = j["dump_outputs"]["arrays"]
+    assert set(d) == {"lcn", "lcn_std", "disparity_index", "best_score", "cost_volume", "config3_geometric_loss"}
+    assert sum(os.path.getsize(tmp_path / (n + ".npy")) for n in d) <= 64e6
+    assert d["cost_volume"]["shape"] == [16, 128, 432, 512] and d["cost_volume"]["sampled"]
+    idx = np.load(tmp_path / "disparity_index.npy")
+    assert idx.dtype == np.float32 and idx.shape == (16, 432, 512) and not d["disparity_index"]["sampled"]
+    assert idx.min() >= 0 and idx.max() <= 127 and (idx == np.round(idx)).all()
+    assert np.isfinite(np.load(tmp_path / "best_score.npy")).all()
+    assert float(np.load(tmp_path / "config3_geometric_loss.npy")) == c3["loss_allgather"][0]
 
 
 def test_two_ranks_self_launched_over_gloo():
