@@ -73,6 +73,9 @@ int argmax_rerank_f32(const float* vol, const float* in0, const float* in1, long
 int rank_tail_f32(const RankPlan& rp, float* vol, const float* in0, const float* in1, long in1_frame_stride,
                   int64_t* idx, float* best, int frames, int D, int H, int W, int bs, hipStream_t stream);
 
+// ncc_fast.hip: compute units of the current device (cached)
+int device_cu_count();
+
 // photometric.hip
 int photometric_fwd_f32(const float* es, const float* ta, float* out, int B, int C, int H, int W, int bs, int type,
                         float eps, hipStream_t s);
@@ -107,6 +110,17 @@ int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, co
 
 int costvol_fast_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W,
                      int D, int bs, int type, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// ranking instantiations of the volume kernels (Top2Planes: ctd_top2.h) and the argmin built on them
+struct Top2Planes;
+bool costvol_rank_supported(int frames, int H, int W, int D, int bs);
+int costvol_rank_f32(const float* im, const float* pat, long pat_frame_stride, const Top2Planes& top, int frames, int H,
+                     int W, int D, int bs, int type, float eps, hipStream_t stream);
+
+// costvol_argmin.hip
+size_t costvol_argmin_workspace_bytes(int frames, int H, int W, int D);
+int costvol_argmin_f32(const float* im, const float* pat, long pat_frame_stride, int64_t* idx, float* best, int frames,
+                       int H, int W, int D, int bs, int type, float eps, float rerank_rel, void* workspace,
+                       size_t workspace_bytes, hipStream_t stream);
 
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

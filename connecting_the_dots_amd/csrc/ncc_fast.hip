@@ -2285,7 +2285,7 @@ struct AlldPlan {
 // `ranked`: the workgroup keeps the ranking of its pixels in LDS (band height limited by the slots, every disparity in one
 // workgroup).  Otherwise the band may be as tall as the image and the passes may be split over workgroups.
 // compute units of the current device (the plan's cost model counts rounds of one workgroup per CU); asked once per device
-static int device_cu_count() {
+int device_cu_count() {
   static int cus[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;

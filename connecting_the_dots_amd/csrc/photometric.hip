@@ -14,20 +14,13 @@
 // visiting (output pixel ascending, tap ascending) -- exactly the order in which the
 // reference's serial CPU loop adds them -- so the result is deterministic, needs no
 // pre-zeroed buffer and no atomics, and is bit-identical to the reference CPU build.
+#include "ctd_costvol_ref.h"
 #include "ctd_internal.h"
 
 namespace ctd {
 
-__device__ inline float t_sqrt(float x) { return sqrtf(x); }
-__device__ inline double t_sqrt(double x) { return sqrt(x); }
 __device__ inline float t_abs(float x) { return fabsf(x); }
 __device__ inline double t_abs(double x) { return fabs(x); }
-
-// h(x) = 0.5 * (1 + x / sqrt(x^2 + eps)); inner part in T, the 0.5 multiply in double (ext.h:249)
-template <typename T>
-__device__ inline T soft_step(T x, T eps) {
-  return (T)(0.5 * (double)((T)1 + x / t_sqrt(x * x + eps)));
-}
 
 template <typename T, int TYPE>
 __global__ __launch_bounds__(256) void photometric_fwd_kernel(const T* __restrict__ es, const T* __restrict__ ta,
@@ -210,31 +203,10 @@ __global__ __launch_bounds__(256) void costvol_kernel(const float* __restrict__ 
   const int h = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int f = blockIdx.z / D, d = blockIdx.z - f * D;
   if (w >= W || h >= H) return;
-  const int half = bs / 2;
-  const float bs2 = (float)(bs * bs);
   const long HW = (long)H * W;
   const float* t = im + (long)f * HW;                       // ta = image
   const float* e = pat + (long)f * pat_frame_stride;        // es = shifted pattern
-  const float ec = e[(long)h * W + clampi(w - d, 0, W - 1)];
-  const float tc = t[(long)h * W + w];
-  float loss = 0.f;
-  for (int bh = 0; bh < bs; ++bh) {
-    const int h0 = clampi(h + bh - half, 0, H - 1);
-    for (int bw = 0; bw < bs; ++bw) {
-      const int w0 = clampi(w + bw - half, 0, W - 1);
-      const float ev = e[(long)h0 * W + clampi(w0 - d, 0, W - 1)];
-      const float tv = t[(long)h0 * W + w0];
-      if (TYPE == 0 || TYPE == 1) {
-        const float diff = ev - tv;
-        if (TYPE == 0) loss += diff * diff / bs2;
-        else loss += fabsf(diff) / bs2;
-      } else {
-        const float diff = soft_step(ev - ec, eps) - soft_step(tv - tc, eps);
-        if (TYPE == 2) loss += diff * diff / bs2;
-        else loss += fabsf(diff) / bs2;
-      }
-    }
-  }
+  const float loss = costvol_ref_cost<TYPE>(t, e, h, w, d, H, W, bs, eps);   // (ctd_costvol_ref.h)
   cost[((long)f * D + d) * HW + (long)h * W + w] = loss;
 }
 

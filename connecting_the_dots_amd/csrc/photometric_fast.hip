@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "ctd_internal.h"
+#include "ctd_top2.h"
 
 namespace ctd {
 
@@ -631,84 +632,107 @@ int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, co
 // so that the image-side soft step of a tap is computed once for 8 disparities.
 // ------------------------------------------------------------------------------------------------------
 constexpr int kCvChunk = 32, kCvD = 8;
-
-template <int TYPE, int BS>
+// RANK (the ranking instantiation of ctd_costvol_argmin_f32): the workgroup walks the kRankChunk / kCvChunk chunks of
+// one ranking chunk (z = frame * n_chunks + ranking chunk), restaging the pattern span per chunk, keeps a Top2 per
+// pixel in registers (each thread owns every disparity of its two pixels: no cross-thread merge) and writes one triple
+// per pixel into `top` instead of the costs.  The costs it ranks are the bits the store instantiation writes.
+template <int TYPE, int BS, bool RANK = false>
 __global__ __launch_bounds__(256) void costvol_fast_kernel(const float* __restrict__ im, const float* __restrict__ pat,
                                                            long pat_frame_stride, float* __restrict__ cost, int H, int W,
-                                                           int D, int n_chunks, float eps) {
+                                                           int D, int n_chunks, float eps, Top2Planes top = {}) {
   constexpr int HALF = BS / 2, TW = kPTW + BS - 1, TH = kPTH + BS - 1, SW = TW + kCvChunk - 1;
+  constexpr int NSUB = RANK ? kRankChunk / kCvChunk : 1;
   __shared__ float sT[TH][TW], sP[TH][SW];
   const int tx = threadIdx.x & 63, ty0 = threadIdx.x >> 6;
   const int x0 = blockIdx.x * kPTW, y0 = blockIdx.y * kPTH;
-  const int f = blockIdx.z / n_chunks, d0 = (blockIdx.z - f * n_chunks) * kCvChunk;
+  const int f = blockIdx.z / n_chunks, chunk = blockIdx.z - f * n_chunks;
   const long HW = (long)H * W;
   stage_tile<BS>(sT, im + (long)f * HW, H, W, x0, y0);
-  // span column s of the tile holds pattern column (x0 - HALF - (kCvChunk - 1)) + s - d0, clamped (the second clamp)
-  const float* p = pat + (long)f * pat_frame_stride;
-  const int span_col0 = x0 - HALF - (kCvChunk - 1) - d0;
-  for (int i = threadIdx.x; i < TH * SW; i += 256) {
-    const int r = i / SW, c = i - r * SW;
-    sP[r][c] = p[(long)clampi(y0 + r - HALF, 0, H - 1) * W + clampi(span_col0 + c, 0, W - 1)];
-  }
-  __syncthreads();
-  const int x = x0 + tx;
-  // first clamp of the tap column, tile relative: tap dx of pixel x sits at image column clamp(x + dx - HALF)
-  int cx[BS];
-#pragma unroll
-  for (int dx = 0; dx < BS; ++dx) cx[dx] = clampi(x + dx - HALF, 0, W - 1) - x0 + HALF + (kCvChunk - 1);
-  for (int db = 0; db < kCvChunk; db += kCvD) {
-    if (d0 + db >= D) break;
-    float acc[2][kCvD], ec[2][kCvD], tc[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      tc[k] = sT[ty0 + 4 * k + HALF][tx + HALF];
-#pragma unroll
-      for (int q = 0; q < kCvD; ++q) {
-        acc[k][q] = 0.f;
-        ec[k][q] = sP[ty0 + 4 * k + HALF][cx[HALF] - (db + q)];    // centre of P_d: P[y][clamp(x - d)]
-      }
+  Top2 best[2] = {top2_empty(), top2_empty()};
+  for (int sub = 0; sub < NSUB; ++sub) {
+    const int d0 = (chunk * NSUB + sub) * kCvChunk;
+    if (RANK) {
+      if (d0 >= D) break;                              // (uniform)
+      if (sub) __syncthreads();                        // everybody is done with the previous span
     }
+    // span column s of the tile holds pattern column (x0 - HALF - (kCvChunk - 1)) + s - d0, clamped (the second clamp)
+    const float* p = pat + (long)f * pat_frame_stride;
+    const int span_col0 = x0 - HALF - (kCvChunk - 1) - d0;
+    for (int i = threadIdx.x; i < TH * SW; i += 256) {
+      const int r = i / SW, c = i - r * SW;
+      sP[r][c] = p[(long)clampi(y0 + r - HALF, 0, H - 1) * W + clampi(span_col0 + c, 0, W - 1)];
+    }
+    __syncthreads();
+    const int x = x0 + tx;
+    // first clamp of the tap column, tile relative: tap dx of pixel x sits at image column clamp(x + dx - HALF)
+    int cx[BS];
+#pragma unroll
+    for (int dx = 0; dx < BS; ++dx) cx[dx] = clampi(x + dx - HALF, 0, W - 1) - x0 + HALF + (kCvChunk - 1);
+    for (int db = 0; db < kCvChunk; db += kCvD) {
+      if (d0 + db >= D) break;
+      float acc[2][kCvD], ec[2][kCvD], tc[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        tc[k] = sT[ty0 + 4 * k + HALF][tx + HALF];
+#pragma unroll
+        for (int q = 0; q < kCvD; ++q) {
+          acc[k][q] = 0.f;
+          ec[k][q] = sP[ty0 + 4 * k + HALF][cx[HALF] - (db + q)];    // centre of P_d: P[y][clamp(x - d)]
+        }
+      }
 #pragma unroll 1
-    for (int dy = 0; dy < BS; ++dy)
+      for (int dy = 0; dy < BS; ++dy)
 #pragma unroll
-      for (int dx = 0; dx < BS; ++dx)
+        for (int dx = 0; dx < BS; ++dx)
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int ty = ty0 + 4 * k;
-          const float t = sT[ty + dy][tx + dx];
-          float tb = 0.f;
-          if (TYPE >= 2) {
-            const float dta = t - tc[k];
-            tb = dta * __builtin_amdgcn_rsqf(fmaf(dta, dta, eps));
+          for (int k = 0; k < 2; ++k) {
+            const int ty = ty0 + 4 * k;
+            const float t = sT[ty + dy][tx + dx];
+            float tb = 0.f;
+            if (TYPE >= 2) {
+              const float dta = t - tc[k];
+              tb = dta * __builtin_amdgcn_rsqf(fmaf(dta, dta, eps));
+            }
+            const float* row = &sP[ty + dy][cx[dx] - db];
+#pragma unroll
+            for (int q = 0; q < kCvD; ++q) {
+              const float e = row[-q];
+              if (TYPE == 0) {
+                const float df = e - t;
+                acc[k][q] = fmaf(df, df, acc[k][q]);
+              } else if (TYPE == 1) {
+                acc[k][q] += fabsf(e - t);
+              } else {
+                const float des = e - ec[k][q];
+                const float d2 = des * __builtin_amdgcn_rsqf(fmaf(des, des, eps)) - tb;   // 2 * (h(des) - h(dta))
+                if (TYPE == 2) acc[k][q] = fmaf(d2, d2, acc[k][q]);
+                else acc[k][q] += fabsf(d2);
+              }
+            }
           }
-          const float* row = &sP[ty + dy][cx[dx] - db];
+      const float scale = (TYPE == 2 ? 0.25f : (TYPE == 3 ? 0.5f : 1.f)) / (float)(BS * BS);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int y = y0 + ty0 + 4 * k;
+        if (x < W && y < H) {
 #pragma unroll
           for (int q = 0; q < kCvD; ++q) {
-            const float e = row[-q];
-            if (TYPE == 0) {
-              const float df = e - t;
-              acc[k][q] = fmaf(df, df, acc[k][q]);
-            } else if (TYPE == 1) {
-              acc[k][q] += fabsf(e - t);
+            const int d = d0 + db + q;
+            if constexpr (RANK) {
+              if (d < D) top2_push(best[k], acc[k][q] * scale, d);           // ascending d
             } else {
-              const float des = e - ec[k][q];
-              const float d2 = des * __builtin_amdgcn_rsqf(fmaf(des, des, eps)) - tb;   // 2 * (h(des) - h(dta))
-              if (TYPE == 2) acc[k][q] = fmaf(d2, d2, acc[k][q]);
-              else acc[k][q] += fabsf(d2);
+              if (d < D) cost[((long)f * D + d) * HW + (long)y * W + x] = acc[k][q] * scale;
             }
           }
         }
-    const float scale = (TYPE == 2 ? 0.25f : (TYPE == 3 ? 0.5f : 1.f)) / (float)(BS * BS);
+      }
+    }
+  }
+  if constexpr (RANK) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const int y = y0 + ty0 + 4 * k;
-      if (x < W && y < H) {
-#pragma unroll
-        for (int q = 0; q < kCvD; ++q) {
-          const int d = d0 + db + q;
-          if (d < D) cost[((long)f * D + d) * HW + (long)y * W + x] = acc[k][q] * scale;
-        }
-      }
+      const int x = x0 + tx, y = y0 + ty0 + 4 * k;
+      if (x < W && y < H) top2_store(top, ((long)f * n_chunks + chunk) * HW + (long)y * W + x, best[k]);
     }
   }
 }
@@ -739,10 +763,15 @@ __device__ inline unsigned sad_u32(unsigned a, unsigned b, unsigned acc) {   // 
   return r;
 }
 
-template <int TYPE, int BS>
+// RANK (the ranking instantiation of ctd_costvol_argmin_f32): the epilogue reduces instead of storing.  Each thread
+// folds its 16 disparities of each of its 4 pixels into a Top2, the two half-waves that share the pixels merge through
+// a lane swap (lane ^ 32: the lower disparities sit in the lower half), the four wavefronts through LDS; the right-most
+// columns' recomputed costs go to LDS and are folded in last.  One triple per (pixel, 128 disparities) leaves for `top`.
+template <int TYPE, int BS, bool RANK = false>
 __global__ __launch_bounds__(256) void costvol_census_kernel(const float* __restrict__ im, const float* __restrict__ pat,
                                                              long pat_frame_stride, float* __restrict__ cost, int H, int W,
-                                                             int D, int n_chunks, float eps) {
+                                                             int D, int n_chunks, float eps, Top2Planes top = {}) {
+  static_assert(kCcD == kRankChunk, "one ranking chunk per workgroup");
   static_assert(TYPE == 2 || TYPE == 3, "census types only");
   constexpr int HALF = BS / 2, TH = kCcR + BS - 1, TW = kCcW + BS - 1;
   constexpr int CPW = kCcW + kCcD;                  // staged pattern census columns j = x' - xp0, j in [0, CPW)
@@ -856,20 +885,47 @@ __global__ __launch_bounds__(256) void costvol_census_kernel(const float* __rest
   const float scale = TYPE == 3 ? 0.5f / (float)(BS * BS) / 8388608.f : 0.25f / (float)(BS * BS);
   const int y = y0 + row, xq = x0 + 4 * q;
   const int x_last_plain = W - 1 - (BS - 1 - HALF);  // right of it the first clamp makes the term depend on d
-  if (y < H) {
+  if constexpr (!RANK) {
+    if (y < H) {
 #pragma unroll
-    for (int k = 0; k < kCcDT; ++k) {
-      const int d = d0 + kCcDT * g + k;
-      if (d >= D) break;
-      float* o = cost + ((long)f * D + d) * HW + (long)y * W + xq;
-      if (xq + 3 <= x_last_plain && (W & 3) == 0 && ((uintptr_t)cost & 15) == 0) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        *(f4*)o = f4{(float)acc[0][k] * scale, (float)acc[1][k] * scale, (float)acc[2][k] * scale, (float)acc[3][k] * scale};
-      } else {
+      for (int k = 0; k < kCcDT; ++k) {
+        const int d = d0 + kCcDT * g + k;
+        if (d >= D) break;
+        float* o = cost + ((long)f * D + d) * HW + (long)y * W + xq;
+        if (xq + 3 <= x_last_plain && (W & 3) == 0 && ((uintptr_t)cost & 15) == 0) {
+          typedef float f4 __attribute__((ext_vector_type(4)));
+          *(f4*)o = f4{(float)acc[0][k] * scale, (float)acc[1][k] * scale, (float)acc[2][k] * scale, (float)acc[3][k] * scale};
+        } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (xq + i <= x_last_plain) o[i] = (float)acc[i][k] * scale;
+          for (int i = 0; i < 4; ++i)
+            if (xq + i <= x_last_plain) o[i] = (float)acc[i][k] * scale;
+        }
       }
+    }
+  }
+  constexpr int NBMAX = HALF > 0 ? HALF : 1;          // right-most columns a tile can hold (BS - 1 - HALF = HALF)
+  __shared__ Top2 red[RANK ? 4 : 1][kCcR][kCcW];
+  __shared__ float bord[RANK ? kCcD : 1][kCcR][NBMAX];
+  if constexpr (RANK) {
+    Top2 tp[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      tp[i] = top2_empty();
+      const bool plain = y < H && xq + i <= x_last_plain;
+#pragma unroll
+      for (int k = 0; k < kCcDT; ++k) {
+        const int d = d0 + kCcDT * g + k;
+        if (plain && d < D) top2_push(tp[i], (float)acc[i][k] * scale, d);   // the bits the store writes, ascending d
+      }
+      Top2 o;
+      o.b1 = __shfl_xor(tp[i].b1, 32);
+      o.i1 = __shfl_xor(tp[i].i1, 32);
+      o.b2 = __shfl_xor(tp[i].b2, 32);
+      tp[i] = top2_merge(tp[i], o);
+    }
+    if ((t & 32) == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[t >> 6][row][4 * q + i] = tp[i];
     }
   }
   // the right-most columns, term by term (ext.h:244-259 order of clamps: tap column first, shift second): the
@@ -894,7 +950,25 @@ __global__ __launch_bounds__(256) void costvol_census_kernel(const float* __rest
           const float d2 = des * __builtin_amdgcn_rsqf(fmaf(des, des, eps)) - dta * __builtin_amdgcn_rsqf(fmaf(dta, dta, eps));
           a = TYPE == 2 ? fmaf(d2, d2, a) : a + fabsf(d2);
         }
-      cost[((long)f * D + d) * HW + (long)yy * W + x] = a * ((TYPE == 2 ? 0.25f : 0.5f) / (float)(BS * BS));
+      const float v = a * ((TYPE == 2 ? 0.25f : 0.5f) / (float)(BS * BS));
+      if constexpr (RANK) bord[dd][r][px] = v;
+      else cost[((long)f * D + d) * HW + (long)yy * W + x] = v;
+    }
+  }
+  if constexpr (RANK) {
+    __syncthreads();
+    if (t < kCcR * kCcW) {
+      const int r = t >> 6, c = t & 63, x = x0 + c, yy = y0 + r;
+      if (x < W && yy < H) {
+        Top2 m = red[0][r][c];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) m = top2_merge(m, red[w][r][c]);
+        if (x >= xb0) {                              // a right-most column: no plain costs were folded in above
+          const int nd = min(kCcD, D - d0);
+          for (int dd = 0; dd < nd; ++dd) top2_push(m, bord[dd][r][x - xb0], d0 + dd);
+        }
+        top2_store(top, ((long)f * n_chunks + blockIdx.z % n_chunks) * HW + (long)yy * W + x, m);
+      }
     }
   }
 }
@@ -951,6 +1025,48 @@ int costvol_fast_f32(const float* im, const float* pat, long pat_frame_stride, f
     case 5: return costvol_fast_type<5>(type, im, pat, pat_frame_stride, cost, frames, H, W, D, eps, stream);
     case 7: return costvol_fast_type<7>(type, im, pat, pat_frame_stride, cost, frames, H, W, D, eps, stream);
     case 9: return costvol_fast_type<9>(type, im, pat, pat_frame_stride, cost, frames, H, W, D, eps, stream);
+    default: return CTD_ERR_UNSUPPORTED;
+  }
+}
+
+// Ranking instantiations of the two volume kernels (ctd_costvol_argmin_f32): one Top2 triple per (pixel, kRankChunk
+// disparities) into `top`, no volume.  SAD / MSE run on the LDS-tiled kernel for every block size (the separable
+// block-9 path has no ranking mode).
+bool costvol_rank_supported(int frames, int H, int W, int D, int bs) {
+  if (bs != 3 && bs != 5 && bs != 7 && bs != 9) return false;
+  if ((double)frames * H * W >= 4294967296.0) return false;            // u32 flat pixel indices on the work list
+  return ceil_div(H, kCcR) <= 65535 && (long)frames * ceil_div(D, kRankChunk) <= 65535;
+}
+
+template <int BS>
+static int costvol_rank_bs(int type, const float* im, const float* pat, long pat_frame_stride, const Top2Planes& top,
+                           int frames, int H, int W, int D, float eps, hipStream_t stream) {
+  const int n_chunks = ceil_div(D, kRankChunk);
+  if (type >= 2) {
+    const dim3 grid(ceil_div(W, kCcW), ceil_div(H, kCcR), frames * n_chunks);
+    if (type == 2)
+      hipLaunchKernelGGL((costvol_census_kernel<2, BS, true>), grid, dim3(256), 0, stream, im, pat, pat_frame_stride, nullptr, H, W, D, n_chunks, eps, top);
+    else
+      hipLaunchKernelGGL((costvol_census_kernel<3, BS, true>), grid, dim3(256), 0, stream, im, pat, pat_frame_stride, nullptr, H, W, D, n_chunks, eps, top);
+  } else {
+    const dim3 grid(ceil_div(W, kPTW), ceil_div(H, kPTH), frames * n_chunks);
+    if (type == 0)
+      hipLaunchKernelGGL((costvol_fast_kernel<0, BS, true>), grid, dim3(256), 0, stream, im, pat, pat_frame_stride, nullptr, H, W, D, n_chunks, eps, top);
+    else
+      hipLaunchKernelGGL((costvol_fast_kernel<1, BS, true>), grid, dim3(256), 0, stream, im, pat, pat_frame_stride, nullptr, H, W, D, n_chunks, eps, top);
+  }
+  CTD_LAUNCH_CHECK();
+  return CTD_OK;
+}
+
+int costvol_rank_f32(const float* im, const float* pat, long pat_frame_stride, const Top2Planes& top, int frames, int H,
+                     int W, int D, int bs, int type, float eps, hipStream_t stream) {
+  if (type < 0 || type > 3) return CTD_ERR_INVALID_ARG;
+  switch (bs) {
+    case 3: return costvol_rank_bs<3>(type, im, pat, pat_frame_stride, top, frames, H, W, D, eps, stream);
+    case 5: return costvol_rank_bs<5>(type, im, pat, pat_frame_stride, top, frames, H, W, D, eps, stream);
+    case 7: return costvol_rank_bs<7>(type, im, pat, pat_frame_stride, top, frames, H, W, D, eps, stream);
+    case 9: return costvol_rank_bs<9>(type, im, pat, pat_frame_stride, top, frames, H, W, D, eps, stream);
     default: return CTD_ERR_UNSUPPORTED;
   }
 }

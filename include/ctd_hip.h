@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -182,6 +182,36 @@ size_t ctd_costvol_workspace_bytes(int frames, int H, int W, int D, int block_si
 int ctd_costvol_fast_f32(const float* im, const float* pattern, long pattern_frame_stride, float* cost,
                     int frames, int H, int W, int D, int block_size, int type, float eps,
                     void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * argmin over the disparities of the SAD / soft-census cost volume, without the volume (additive in ABI version 5).
+ *   Arguments as ctd_costvol_fast_f32 (pattern_frame_stride 0 or H * W), outputs idx int64 [frames][H][W] and best f32
+ *   [frames][H][W] (may be NULL).  Nothing of size frames * D * H * W is written.
+ *   idx == torch.argmin(V, 1) bit for bit, first index on ties, V = the ctd_costvol_f32 volume of the same arguments.
+ * How: the tolerance-level volume kernel (census transform for the census types, the LDS-tiled kernel for SAD / MSE, all
+ * block sizes) ranks its costs instead of storing them: per pixel and 128 disparities the best fast cost b1, its first
+ * index i1 and the runner-up b2.  A pixel's fast winner is accepted when
+ *     b2 - b1 > rerank_rel * (b1 + b2) + 2e-6
+ * which, under the fast bound |fast - exact| <= rerank_rel |exact| + 1e-6, implies exact(i1) < exact(d) for every other d
+ * (costvol_argmin.hip has the derivation); every other pixel (exact ties included) is re-scored: all D costs in the
+ * reference order, first-index argmin.
+ *   rerank_rel: 1e-5 (the default of the Python wrapper) = the bound ctd_costvol_fast_f32 documents; larger values
+ *     re-score more pixels; < 0 = plain argmin of the fast costs, nothing re-scored (indices may then differ from V's
+ *     where two costs lie within the bound); NaN = CTD_ERR_INVALID_ARG.
+ *   best: for a re-scored pixel the reference-order cost V[f][idx][h][w], bit for bit; for every other pixel the fast
+ *     cost of idx, within 1e-5 |V| + 1e-6.
+ * Workspace: ctd_costvol_argmin_workspace_bytes() bytes, 256-byte aligned, O(frames * H * W * ceil(D / 128)):
+ *   bytes [0, 4): u32 number n of re-scored pixels (0 when rerank_rel < 0),
+ *   bytes [256, 256 + 4 n): their flat indices f * H * W + h * W + w (u32, order unspecified), then the rank triples.
+ * Errors, before any HIP call: an even block size, a type outside 0..3 or a stride other than 0 / H * W is
+ * CTD_ERR_INVALID_ARG; block sizes other than 3/5/7/9, frames * H * W >= 2^32 or grids beyond the launch limits are
+ * CTD_ERR_UNSUPPORTED (compose ctd_costvol_f32 and an argmin then).  The workspace query returns 0 for both and for
+ * frames == 0.
+ * -------------------------------------------------------------------------------------- */
+size_t ctd_costvol_argmin_workspace_bytes(int frames, int H, int W, int D, int block_size, int type, int per_frame_pattern);
+int ctd_costvol_argmin_f32(const float* im, const float* pattern, long pattern_frame_stride,
+                           int64_t* idx, float* best, int frames, int H, int W, int D, int block_size, int type,
+                           float eps, float rerank_rel, void* workspace, size_t workspace_bytes, int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
