@@ -120,17 +120,25 @@ __constant__ float kSobel[5][5] = {{-5.f / 240, -4.f / 240, 0.f, 4.f / 240, 5.f 
                                    {-5.f / 240, -4.f / 240, 0.f, 4.f / 240, 5.f / 240}};
 constexpr float kB0 = 0.0503428816795f, kB1 = 1.07274045944f;   // networks.py:389-390
 
+// kx is odd in j (kx[i][4-j] = -kx[i][j], kx[i][2] = 0) and ky = kx^T odd in i: the sums run over differences of
+// mirrored taps, so a locally flat disparity gives exactly 0 (summing the 25 rounded products left a residue of
+// ~1e-7 |disp|, which the direction gx / g of the backward amplifies where g sits near its 1e-4 floor)
 __device__ inline void sobel_at(const float* __restrict__ x, int H, int W, int h, int w, float& gx, float& gy) {
-  gx = 0.f;
-  gy = 0.f;
+  float v[5][5];
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int hh = clampi(h + i - 2, 0, H - 1);
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const float v = x[(long)hh * W + clampi(w + j - 2, 0, W - 1)];
-      gx = fmaf(kSobel[i][j], v, gx);
-      gy = fmaf(kSobel[j][i], v, gy);
+    for (int j = 0; j < 5; ++j) v[i][j] = x[(long)hh * W + clampi(w + j - 2, 0, W - 1)];
+  }
+  gx = 0.f;
+  gy = 0.f;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      gx = fmaf(kSobel[i][j], v[i][j] - v[i][4 - j], gx);
+      gy = fmaf(kSobel[i][j], v[j][i] - v[4 - j][i], gy);
     }
   }
 }
@@ -295,8 +303,10 @@ __device__ inline GeoPoint geo_forward(const Pose& P, const float* __restrict__ 
   const float u = g.uvd[0] / g.den, v = g.uvd[1] / g.den;
   const float un = 2.f * (u / (float)(W - 1) - 0.5f), vn = 2.f * (v / (float)(H - 1) - 0.5f);
   float ix = ((un + 1.f) * (float)W - 1.f) * 0.5f, iy = ((vn + 1.f) * (float)H - 1.f) * 0.5f;   // align_corners=False
-  g.clip_x = !(ix >= 0.f && ix <= (float)(W - 1));      // border padding clips the coordinate, gradient 0 there
-  g.clip_y = !(iy >= 0.f && iy <= (float)(H - 1));
+  // border padding clips the coordinate; as in ATen's clip_coordinates_set_grad the borders themselves count as out of
+  // bounds, so the position gradient is 0 at ix == 0 and ix == W-1 exactly too (the sampled value is the same either way)
+  g.clip_x = !(ix > 0.f && ix < (float)(W - 1));
+  g.clip_y = !(iy > 0.f && iy < (float)(H - 1));
   ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
   iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
   g.ix = ix;

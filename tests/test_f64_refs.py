@@ -1,0 +1,136 @@
+"""The float64 references of tests/f64_refs.py against the values and autograd gradients captured from the reference
+modules (tests/golden/losses.npz, pattern_loss.npz), on the CPU.  The goldens are ATen f32; the tolerances are the
+ones tests/test_losses_gpu.py and tests/test_pattern_loss_gpu.py hold the HIP kernels to against the same goldens, so
+a reference that passes here restates the reference modules (and not the kernels' own formulas) to within the goldens'
+f32 rounding."""
+import numpy as np
+import pytest
+import torch
+
+from tests import f64_refs as R
+from tests.util import assert_close, golden
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def test_disp_to_depth_ref():
+    g = golden("losses")
+    ref = R.disp_to_depth(t(g["d2d_disp"]), float(g["d2d_bf"]), t(g["d2d_go"]))
+    assert ref.value.dtype == torch.float64
+    assert_close(ref.value.numpy(), g["d2d_depth"], rtol=1e-6, atol=0, what="depth")
+    assert_close(ref.grads["disp"].numpy(), g["d2d_grad"], rtol=2e-6, atol=0, what="grad")
+    assert (ref.grads["disp"][t(g["d2d_disp"]) <= 0] == 0).all()
+
+
+def test_sobel_ref():
+    g = golden("losses")
+    gx, gy = R.sobel(t(g["dl_disp"]).double())
+    # the golden's f32 sums run over disparities up to ~70 (ulp 7.6e-6)
+    assert_close(torch.cat((gx, gy), 1).numpy(), g["sobel_grad"], rtol=1e-5, atol=1e-5, what="sobel")
+
+
+def test_disparity_loss_ref_with_edge():
+    g = golden("losses")
+    ref = R.disparity_loss(t(g["dl_disp"]), t(g["dl_edge"]))
+    assert_close(float(ref.value), g["dl_val"], rtol=1e-5, atol=0, what="value")
+    assert_close(ref.grads["disp"].numpy(), g["dl_gdisp"], rtol=1e-4, atol=1e-8, what="grad disp")
+    assert_close(ref.grads["edge"].numpy(), g["dl_gedge"], rtol=1e-4, atol=1e-9, what="grad edge")
+
+
+def test_disparity_loss_ref_without_edge():
+    g = golden("losses")
+    ref = R.disparity_loss(t(g["dl_disp"]))
+    assert_close(float(ref.value), g["dl_noedge_val"], rtol=1e-5, atol=0, what="value")
+    assert_close(ref.grads["disp"].numpy(), g["dl_noedge_gdisp"], rtol=1e-4, atol=1e-8, what="grad disp")
+
+
+def test_disparity_loss_ref_logits_chain():
+    """edge = 1 - sigmoid(logits): the logits gradient is the edge gradient times -sigmoid'"""
+    g = golden("losses")
+    e = t(g["dl_edge"]).double().clamp(1e-6, 1 - 1e-6)
+    logits = torch.log((1 - e) / e)                          # 1 - sigmoid(logits) == e
+    ref = R.disparity_loss(t(g["dl_disp"]), logits=logits)
+    s = torch.sigmoid(logits)
+    ref_e = R.disparity_loss(t(g["dl_disp"]), edge=1 - s)
+    assert torch.allclose(ref.value, ref_e.value, rtol=1e-12, atol=0)
+    assert torch.allclose(ref.grads["logits"], -ref_e.grads["edge"] * s * (1 - s), rtol=1e-9, atol=1e-15)
+    assert_close(ref.grads["disp"].numpy(), g["dl_gdisp"], rtol=1e-4, atol=1e-8, what="grad disp")
+
+
+@pytest.mark.parametrize("tag,clamp", [("c", 0.1), ("nc", -1.0)])
+def test_geometric_loss_ref(tag, clamp):
+    g = golden("losses")
+    a = {n: t(g["ge_" + n]) for n in ("depth0", "depth1", "K", "R0", "t0", "R1", "t1")}
+    ray = t(g["ge_ray"][0])
+    ref = R.geometric_loss(a["depth0"], a["depth1"], a["K"], ray, a["R0"], a["t0"], a["R1"], a["t1"], clamp)
+    assert_close(float(ref.value), g["ge_%s_val" % tag], rtol=2e-5, atol=0, what="value")
+    assert_close(ref.grads["depth0"].numpy(), g["ge_%s_g0" % tag], rtol=2e-3, atol=2e-7, what="grad depth0")
+    assert_close(ref.grads["depth1"].numpy(), g["ge_%s_g1" % tag], rtol=2e-3, atol=2e-7, what="grad depth1")
+    # one direction and its intermediates: ProjectionBaseLoss's uv and d, the un-normalised sampling coordinates
+    B, _, H, W = g["ge_depth0"].shape
+    fwd = ref.inter["fwd"]
+    assert_close(fwd["d"].reshape(B, -1, 1).numpy(), g["ge_d"], rtol=1e-5, atol=1e-6, what="d")
+    u = (2 * fwd["ix"] + 1) / W * (W - 1) / 2                   # invert the align_corners=False unnormalisation
+    v = (2 * fwd["iy"] + 1) / H * (H - 1) / 2
+    assert_close(torch.stack((u.reshape(B, -1), v.reshape(B, -1)), 2).numpy(), g["ge_uv"], rtol=1e-5, atol=1e-4,
+                 what="uv")
+    with torch.no_grad():
+        dd = {k: x.double() for k, x in a.items()}
+        v01, _ = R.geometric_dir(dd["depth0"], dd["depth1"], dd["K"], ray.double(), dd["R0"], dd["t0"], dd["R1"],
+                                 dd["t1"], clamp)
+    assert_close(float(v01), g["ge_%s_fwd01" % tag], rtol=2e-5, atol=0, what="one direction")
+    assert torch.equal(fwd["diff"], fwd["e"].abs())
+
+
+@pytest.mark.parametrize("name", ["census_sad", "mse"])
+@pytest.mark.parametrize("use_std", [True, False])
+def test_pattern_loss_ref(name, use_std):
+    g = golden("pattern_loss")
+    ref = R.pattern_loss(t(g["disp"]), t(g["im"]), t(g["pattern"]), t(g["std"]) if use_std else None, name, 0.5)
+    val, proj = ref.value
+    tag = "%s_%d" % (name, use_std)
+    assert_close(proj.numpy(), g["proj_" + tag], rtol=1e-5, atol=2e-5, what="proj " + tag)
+    assert_close(float(val), g["val_" + tag], rtol=1e-4, atol=0, what="val " + tag)
+    assert_close(ref.grads["disp"].numpy(), g["gdisp_" + tag], rtol=2e-3, atol=2e-6, what="grad " + tag)
+    B, _, H, W = g["disp"].shape
+    assert ref.inter["pair"].shape == (B, 81, H, W)
+    assert_close(ref.inter["ix"].numpy(), np.arange(W) * W / (W - 1) - 0.5 - g["disp"].astype(np.float64) * W / (W - 1), rtol=0,
+                 atol=1e-9, what="ix")
+
+
+def test_pattern_loss_ref_upstream_proj_gradient_and_frames():
+    """grad_proj adds grad_proj . d proj / d disp; a batch equals its frames run with the shared denominator"""
+    g = golden("pattern_loss")
+    disp, im, pat, std = (t(g[k]) for k in ("disp", "im", "pattern", "std"))
+    gp = torch.from_numpy(np.random.RandomState(3).randn(*g["disp"].shape))
+    a = R.pattern_loss(disp, im, pat, std, "census_sad", 0.5)
+    b = R.pattern_loss(disp, im, pat, std, "census_sad", 0.5, grad_proj=gp)
+    d = disp.double().requires_grad_(True)
+    grid, _, _ = R.warp_grid(d, *disp.shape[2:])
+    proj = torch.nn.functional.grid_sample(pat.double().mean(1, keepdim=True).expand(2, -1, -1, -1), grid,
+                                           padding_mode="border", align_corners=False)
+    (gproj,) = torch.autograd.grad((proj * gp).sum(), d)
+    assert torch.allclose(b.grads["disp"], a.grads["disp"] + gproj, rtol=1e-10, atol=1e-14)
+    # whole-batch composition in one graph
+    d = disp.double().requires_grad_(True)
+    grid, _, _ = R.warp_grid(d, *disp.shape[2:])
+    proj = torch.nn.functional.grid_sample(pat.double().mean(1, keepdim=True).expand(2, -1, -1, -1), grid,
+                                           padding_mode="border", align_corners=False)
+    diff, _ = R.block_loss(proj, im.double(), 9, "census_sad", 0.5)
+    val = (std.double() * diff).sum() / std.double().sum()
+    (gd,) = torch.autograd.grad(val, d)
+    assert torch.allclose(a.grads["disp"], gd, rtol=1e-10, atol=1e-14)
+    assert torch.allclose(a.value[0], val.detach(), rtol=1e-12, atol=0)
+
+
+def test_block_loss_ref_matches_package_composition():
+    """the four loss types against photometric_loss_pytorch, the package's stock-torch formulation"""
+    from connecting_the_dots_amd.torchext.functions import photometric_loss_pytorch
+    rs = np.random.RandomState(7)
+    es, ta = torch.from_numpy(rs.randn(2, 1, 13, 21)), torch.from_numpy(rs.randn(2, 1, 13, 21))
+    for name in R.PHOTO_TYPES:
+        got, pair = R.block_loss(es, ta, 9, name, 0.5)
+        assert torch.allclose(got, photometric_loss_pytorch(es, ta, 9, name, 0.5), rtol=1e-12, atol=1e-15), name
+        assert pair.shape == (2, 81, 13, 21)
