@@ -435,6 +435,46 @@ int ctd_costvol_argmin_f32(const float* im, const float* pattern, long pattern_f
                             rerank_rel, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t ctd_xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, int block_size, int per_frame_pattern) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0) return 0;
+  return xcorrvol_subpixel_workspace_bytes(frames, H, W, D, per_frame_pattern != 0);
+}
+
+int ctd_xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                              float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int mode,
+                              void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const bool prepared = (mode & CTD_PATTERN_PREPARED) != 0;
+  mode &= ~CTD_PATTERN_PREPARED;
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0 ||
+      (mode != CTD_SUBPIXEL_PARABOLA && mode != CTD_SUBPIXEL_EQUIANGULAR))
+    return CTD_ERR_INVALID_ARG;
+  if (in1_frame_stride != 0 && in1_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !idx || !disp) return CTD_ERR_INVALID_ARG;
+  if (!workspace || ((uintptr_t)workspace & 255) ||
+      workspace_bytes < xcorrvol_subpixel_workspace_bytes(frames, H, W, D, in1_frame_stride != 0))
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return xcorrvol_subpixel_f32(in0, in1, in1_frame_stride, idx, disp, refined, frames, H, W, D, block_size, mode,
+                               prepared, workspace, (hipStream_t)stream);
+}
+
+int ctd_costvol_subpixel_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
+                             float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int type,
+                             float eps, int mode, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0 || type < 0 || type > 3 ||
+      (mode != CTD_SUBPIXEL_PARABOLA && mode != CTD_SUBPIXEL_EQUIANGULAR))
+    return CTD_ERR_INVALID_ARG;
+  if (pattern_frame_stride != 0 && pattern_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !idx || !disp) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return costvol_subpixel_f32(im, pattern, pattern_frame_stride, idx, disp, refined, frames, H, W, D, block_size, type,
+                              eps, mode, (hipStream_t)stream);
+}
+
 int ctd_disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float baseline_focal, int device, void* stream) {
   if (n < 0) return CTD_ERR_INVALID_ARG;
   if (n == 0) return CTD_OK;

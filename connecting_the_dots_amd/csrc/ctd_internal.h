@@ -122,6 +122,15 @@ int costvol_argmin_f32(const float* im, const float* pat, long pat_frame_stride,
                        int H, int W, int D, int bs, int type, float eps, float rerank_rel, void* workspace,
                        size_t workspace_bytes, hipStream_t stream);
 
+// subpixel.hip
+size_t xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern);
+int xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx, float* disp,
+                          uint8_t* refined, int frames, int H, int W, int D, int bs, int mode, bool prepared,
+                          void* workspace, hipStream_t stream);
+int costvol_subpixel_f32(const float* im, const float* pat, long pat_frame_stride, const int64_t* idx, float* disp,
+                         uint8_t* refined, int frames, int H, int W, int D, int bs, int type, float eps, int mode,
+                         hipStream_t stream);
+
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

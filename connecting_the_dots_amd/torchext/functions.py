@@ -273,6 +273,7 @@ class PreparedPattern:
 
     def __init__(self, in1, n_frames, n_disps, block_size, workspace):
         self.in1, self.n_frames, self.n_disps, self.block_size, self.workspace = in1, n_frames, n_disps, block_size, workspace
+        self.subpixel = {}            # (H, W, D, block_size) -> workspace of xcorrvol_subpixel, pattern planes filled
 
 
 def prepare_pattern(in1, n_frames, n_disps, block_size):
@@ -295,12 +296,19 @@ def prepare_pattern(in1, n_frames, n_disps, block_size):
     return PreparedPattern(in1, N, D, bs, ws)
 
 
-def xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume=False, algo=None, rerank_eps=1e-5, prepared=None):
+def xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume=False, algo=None, rerank_eps=1e-5, prepared=None,
+                    subpixel=None):
     """Additive: fused NCC volume + argmax over disparity (C == 1).
     in0 [N,1,H,W] | [1,H,W]; in1 [1,H,W] | [N,1,H,W].
     Returns (idx int64, best f32[, volume]); idx == torch.argmax(xcorrvol(...), 0) of the reference.
     `prepared`: a `prepare_pattern` handle of the same `in1`, frame count and shape (fast path only): the pattern half of
-    the pre-pass is skipped and the handle's workspace is used."""
+    the pre-pass is skipped and the handle's workspace is used.
+    subpixel: None (default) | "parabola" | "equiangular": also return (disp f32, refined u8) of
+    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple."""
+    if subpixel is not None:
+        _subpixel_mode(subpixel, "xcorrvol_argmax")
+        out = xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume, algo, rerank_eps, prepared)
+        return tuple(out) + xcorrvol_subpixel(in0, in1, out[0], n_disps, block_size, subpixel, prepared)
     _check(in0, "in0", (torch.float32,))
     _check(in1, "in1", (torch.float32,))
     squeeze = in0.dim() == 3
@@ -369,13 +377,20 @@ def lcn(data, radius, epsilon, algo=None):
 
 
 def lcn_xcorrvol_argmax(raw, in1, n_disps, block_size, radius=5, epsilon=0.05, return_volume=False, lcn_algo="exact",
-                        rerank_eps=1e-5, prepared=None):
+                        rerank_eps=1e-5, prepared=None, subpixel=None):
     """Additive: `lcn` of the raw frames, then `xcorrvol_argmax(..., algo='fast')` against the (already LCN'd) pattern,
     as ONE call whose first kernel streams the raw frames once and leaves both the LCN outputs and the matcher's window
     statistics (ctd_lcn_xcorrvol_argmax_f32).  raw [N,1,H,W]; in1 [1,H,W] | [N,1,H,W].
     Returns (lcn, std, idx, best[, volume]).  lcn_algo 'exact': lcn / std carry the bits of `lcn(..., algo='exact')`;
     'fast': f32 box sums, tolerance level on well-conditioned windows only (see include/ctd_hip.h).
-    Shapes the fused kernel does not cover run the two calls it replaces."""
+    Shapes the fused kernel does not cover run the two calls it replaces.
+    subpixel: None (default) | "parabola" | "equiangular": also return (disp, refined) of
+    `xcorrvol_subpixel(lcn, in1, idx, ...)` -- against the LCN output this call returns -- at the end of the tuple."""
+    if subpixel is not None:
+        _subpixel_mode(subpixel, "lcn_xcorrvol_argmax")
+        out = lcn_xcorrvol_argmax(raw, in1, n_disps, block_size, radius, epsilon, return_volume, lcn_algo, rerank_eps,
+                                  prepared)
+        return tuple(out) + xcorrvol_subpixel(out[0], in1, out[2], n_disps, block_size, subpixel, prepared)
     _check(raw, "raw", (torch.float32,))
     _check(in1, "in1", (torch.float32,))
     if raw.dim() != 4 or raw.shape[1] != 1 or in1.dim() not in (3, 4):
@@ -697,7 +712,8 @@ def costvol(im, pattern, n_disps, block_size, type='sad', eps=0.1, algo=None):
     return out[0] if squeeze else out
 
 
-def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1, rerank_rel=1e-5, return_rescored=False):
+def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1, rerank_rel=1e-5, return_rescored=False,
+                   subpixel=None):
     """Additive: the disparity of least SAD / MSE / soft-census block cost without the cost volume.
     im [N,H,W] | [H,W] f32, pattern [H,W] | [N,H,W] (as `costvol`) -> (idx int64, best f32), each [N,H,W] | [H,W].
     idx equals torch.argmin(costvol(..., algo="exact"), 1) bit for bit (first index on ties): the fast volume kernel
@@ -708,7 +724,13 @@ def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1,
     fast costs, nothing re-scored (indices may then differ from the exact volume's on near-ties).
     return_rescored: also return the sorted int64 flat indices (f*H*W + h*W + w) of the re-scored pixels.
     Block sizes the kernels do not cover (odd, > 9) fall back to costvol(algo="exact") + torch.argmin (all pixels then
-    count as re-scored)."""
+    count as re-scored).
+    subpixel: None (default) | "equiangular" | "parabola": also return (disp, refined) of
+    `costvol_subpixel(im, pattern, idx, ...)` at the end of the tuple (no accuracy gain for the census types)."""
+    if subpixel is not None:
+        _subpixel_mode(subpixel, "costvol_argmin")
+        out = costvol_argmin(im, pattern, n_disps, block_size, type, eps, rerank_rel, return_rescored)
+        return tuple(out) + costvol_subpixel(im, pattern, out[0], n_disps, block_size, type, eps, subpixel)
     _check(im, "im", (torch.float32,))
     _check(pattern, "pattern", (torch.float32,))
     type = type.lower()
@@ -748,6 +770,117 @@ def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1,
     if squeeze:
         idx, best = idx[0], best[0]
     return (idx, best, rescored) if return_rescored else (idx, best)
+
+
+_SUBPIXEL_MODES = {"parabola": 0, "equiangular": 1}
+
+_SUBPIXEL_RULE = """
+    The rule (include/ctd_hip.h, word for word there), in float32, no FMA, IEEE divide, around d = idx:
+      NCC, a maximum (sm, s0, sp = the exact scores at d-1, d, d+1):
+        parabola:    den = (sm - s0) + (sp - s0); refined iff den < 0, delta = 0.5 * ((sm - sp) / den)
+        equiangular: sp > sm: delta = 0.5 * ((sp - sm) / (s0 - sm)), refined iff s0 - sm > 0;
+                     else:    delta = 0.5 * ((sp - sm) / (s0 - sp)), refined iff s0 - sp > 0
+      costs, a minimum (cm, c0, cp = the exact costs at d-1, d, d+1):
+        parabola:    den = (cm - c0) + (cp - c0); refined iff den > 0, delta = 0.5 * ((cm - cp) / den)
+        equiangular: cp < cm: delta = 0.5 * ((cm - cp) / (cm - c0)), refined iff cm - c0 > 0;
+                     else:    delta = 0.5 * ((cm - cp) / (cp - c0)), refined iff cp - c0 > 0
+      delta is clamped to [-0.5, 0.5]; disp = d + delta where refined, d where not (d == 0, d == D-1, flat windows);
+      idx outside [0, D) gives disp = NaN, refined = 0."""
+
+
+def _subpixel_mode(mode, who):
+    if mode not in _SUBPIXEL_MODES:
+        raise RuntimeError("%s: unknown sub-pixel mode %r (parabola | equiangular)" % (who, mode))
+    return _SUBPIXEL_MODES[mode]
+
+
+def _subpixel_outputs(idx):
+    _check(idx, "idx", (torch.int64,))
+    return torch.empty(idx.shape, dtype=torch.float32, device=idx.device), \
+        torch.empty(idx.shape, dtype=torch.uint8, device=idx.device)
+
+
+def xcorrvol_subpixel(in0, in1, idx, n_disps, block_size, mode="parabola", prepared=None):
+    """Additive: sub-pixel refinement of NCC matcher indices -> (disp f32, refined u8), shaped as idx.
+    in0 [N,1,H,W] | [1,H,W] and in1 [1,H,W] | [N,1,H,W] as `xcorrvol_argmax` takes them, idx int64 [N,H,W] | [H,W] as it
+    returns them (any index: it need not be the argmax).  The fit runs through the scores of
+    `xcorrvol(..., algo="exact")` -- the reference's bits -- at idx - 1, idx, idx + 1 (ctd_xcorrvol_subpixel_f32).
+    mode: "parabola" (default; measured the better fit for NCC) | "equiangular".
+    `prepared`: a `prepare_pattern` handle of the same in1 and shape keeps the pattern's window statistics of this op
+    too, computed at its first use, so later calls recompute the frame half only.
+    Use: disp_to_depth(disp + disp_offset, baseline_focal)."""
+    _check(in0, "in0", (torch.float32,))
+    _check(in1, "in1", (torch.float32,))
+    m = _subpixel_mode(mode, "xcorrvol_subpixel")
+    squeeze = in0.dim() == 3
+    a0 = in0.unsqueeze(0) if squeeze else in0
+    if a0.dim() != 4 or a0.shape[1] != 1 or in1.dim() not in (3, 4):
+        raise RuntimeError("xcorrvol_subpixel expects in0 [N,1,H,W] or [1,H,W] and in1 [1,H,W] or [N,1,H,W]")
+    dev = _same_device(a0, in1, idx)
+    N, C, H, W = a0.shape
+    if tuple(in1.shape[-3:]) != (C, H, W) or (in1.dim() == 4 and in1.shape[0] != N):
+        raise RuntimeError("xcorrvol_subpixel: in1 does not match in0")
+    if tuple(idx.shape) != ((H, W) if squeeze else (N, H, W)):
+        raise RuntimeError("xcorrvol_subpixel: idx must be shaped as xcorrvol_argmax returns it")
+    disp, refined = _subpixel_outputs(idx)
+    stride1 = 0 if in1.dim() == 3 else H * W
+    D, bs = int(n_disps), int(block_size)
+    L = _lib.lib()
+    nws = L.ctd_xcorrvol_subpixel_workspace_bytes(N, H, W, D, bs, 1 if stride1 else 0)
+    flag = 0
+    if prepared is not None:
+        if prepared.in1 is not in1 or prepared.n_frames != N or prepared.workspace.device != dev:
+            raise RuntimeError("xcorrvol_subpixel: `prepared` belongs to another pattern, frame count or device")
+        key = (H, W, D, bs)
+        ws = prepared.subpixel.get(key)
+        if ws is None:
+            ws = prepared.subpixel[key] = _workspace(nws, dev)
+        else:
+            flag = 0x100                                                # CTD_PATTERN_PREPARED: the pattern planes are in ws
+    else:
+        ws = _workspace(nws, dev)
+    st = L.ctd_xcorrvol_subpixel_f32(_ptr(a0), _ptr(in1), stride1, _ptr(idx), _ptr(disp), _ptr(refined), N, H, W, D, bs,
+                                     m | flag, _ptr(ws), ws.numel(), dev.index, _stream(dev))
+    if st != 0 and flag == 0 and prepared is not None:
+        prepared.subpixel.pop((H, W, D, bs), None)                      # the planes were not written
+    _lib.check(st, "xcorrvol_subpixel")
+    return disp, refined
+
+
+def costvol_subpixel(im, pattern, idx, n_disps, block_size, type='census_sad', eps=0.1, mode="equiangular"):
+    """Additive: sub-pixel refinement of cost-volume indices -> (disp f32, refined u8), shaped as idx.
+    im [N,H,W] | [H,W] and pattern [H,W] | [N,H,W] as `costvol_argmin` takes them, idx int64 shaped as it returns it.
+    The fit runs through the costs of `costvol(..., algo="exact")` at idx - 1, idx, idx + 1
+    (ctd_costvol_subpixel_f32).  mode: "equiangular" (default; measured the better fit for SAD) | "parabola".
+    The soft-census types (census_mse, census_sad) are refined by the same rule, bit for bit, but their costs are too
+    non-linear in d for either fit to improve accuracy: refine SAD / MSE or NCC instead."""
+    _check(im, "im", (torch.float32,))
+    _check(pattern, "pattern", (torch.float32,))
+    m = _subpixel_mode(mode, "costvol_subpixel")
+    type = type.lower()
+    if type not in _PHOTO_TYPES:
+        raise RuntimeError("costvol_subpixel: invalid loss type %r" % (type,))
+    squeeze = im.dim() == 2
+    a = im.unsqueeze(0) if squeeze else im
+    if a.dim() != 3 or pattern.dim() not in (2, 3) or tuple(pattern.shape[-2:]) != tuple(a.shape[-2:]):
+        raise RuntimeError("costvol_subpixel expects im [N,H,W] or [H,W] and pattern [H,W] or [N,H,W]")
+    dev = _same_device(a, pattern, idx)
+    N, H, W = a.shape
+    if pattern.dim() == 3 and pattern.shape[0] != N:
+        raise RuntimeError("costvol_subpixel: pattern batch does not match im")
+    if tuple(idx.shape) != tuple(im.shape):
+        raise RuntimeError("costvol_subpixel: idx must be shaped as costvol_argmin returns it")
+    disp, refined = _subpixel_outputs(idx)
+    stride = 0 if pattern.dim() == 2 else H * W
+    st = _lib.lib().ctd_costvol_subpixel_f32(_ptr(a), _ptr(pattern), stride, _ptr(idx), _ptr(disp), _ptr(refined), N, H,
+                                             W, int(n_disps), int(block_size), _PHOTO_TYPES[type], float(eps), m,
+                                             dev.index, _stream(dev))
+    _lib.check(st, "costvol_subpixel")
+    return disp, refined
+
+
+xcorrvol_subpixel.__doc__ += _SUBPIXEL_RULE
+costvol_subpixel.__doc__ += _SUBPIXEL_RULE
 
 
 # --------------------------------------------------------------------------------------

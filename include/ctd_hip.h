@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -212,6 +212,48 @@ size_t ctd_costvol_argmin_workspace_bytes(int frames, int H, int W, int D, int b
 int ctd_costvol_argmin_f32(const float* im, const float* pattern, long pattern_frame_stride,
                            int64_t* idx, float* best, int frames, int H, int W, int D, int block_size, int type,
                            float eps, float rerank_rel, void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * Sub-pixel refinement of a matcher index (additive in ABI version 5): a parabola or equiangular fit through the
+ * reference-order scores at d-1, d, d+1 around d = idx[f][h][w].
+ *   NCC:   the scores of ctd_xcorrvol_f32(CTD_NCC_EXACT) (bit-identical to the reference), a maximum; C == 1.
+ *   Costs: the costs of ctd_costvol_f32 of the same arguments, a minimum.
+ * The refined disparity is a function of these three volume entries alone, evaluated in float32 in this order (no FMA,
+ * IEEE divide):
+ *   NCC (maximum; sm, s0, sp = exact scores at d-1, d, d+1):
+ *     parabola:    den = (sm - s0) + (sp - s0); refined iff den < 0, then delta = 0.5f * ((sm - sp) / den)
+ *     equiangular: if sp > sm: delta = 0.5f * ((sp - sm) / (s0 - sm)), refined iff s0 - sm > 0
+ *                  else:       delta = 0.5f * ((sp - sm) / (s0 - sp)), refined iff s0 - sp > 0
+ *   Costs (minimum; cm, c0, cp = exact costs at d-1, d, d+1):
+ *     parabola:    den = (cm - c0) + (cp - c0); refined iff den > 0, then delta = 0.5f * ((cm - cp) / den)
+ *     equiangular: if cp < cm: delta = 0.5f * ((cm - cp) / (cm - c0)), refined iff cm - c0 > 0
+ *                  else:       delta = 0.5f * ((cm - cp) / (cp - c0)), refined iff cp - c0 > 0
+ *   For both families: delta is clamped to [-0.5f, 0.5f] (this only matters when idx is not the exact argmax / argmin,
+ *   e.g. with rerank_eps < 0); disp = (float)d + delta where refined, (float)d where not (the not-refined cases include
+ *   d == 0, d == D-1 and 0/0 on flat windows); an idx outside [0, D) gives disp = NaN and refined = 0 and is never
+ *   used to read.
+ * Outputs disp f32 [frames][H][W] and refined u8 [frames][H][W] (may be NULL).  idx int64 [frames][H][W].
+ * The soft-census costs are too non-linear in d for either fit to improve accuracy; their refinement is defined (and
+ * tested bit for bit) but not recommended.
+ * mode: CTD_SUBPIXEL_PARABOLA or CTD_SUBPIXEL_EQUIANGULAR.  For the NCC call mode may carry CTD_PATTERN_PREPARED: the
+ *   workspace then already holds the pattern planes of an earlier call with the same in1, frames, H, W, D, block_size
+ *   and stride, and only the frame half is recomputed.
+ * Workspace (NCC only): ctd_xcorrvol_subpixel_workspace_bytes() bytes, 256-byte aligned: the quotients x / bs^2 of the
+ *   frames and the pattern(s), and (mean, sum of squared deviations) of every pattern window centre x in [-(D-1), W-1].
+ * Errors, before any HIP call (CTD_ERR_INVALID_ARG): an even or < 1 block size, a mode outside {0, 1}, a type outside
+ * 0..3, a stride other than 0 / H * W, D < 1, H or W < 1, frames < 0, D * H * W >= 2^31, a NULL in0 / in1 / im /
+ * pattern / idx / disp, or a workspace that is NULL, too small or not 256-byte aligned.  frames == 0 is CTD_OK.  The
+ * workspace query returns 0 for invalid shapes and for frames == 0.
+ * -------------------------------------------------------------------------------------- */
+#define CTD_SUBPIXEL_PARABOLA 0
+#define CTD_SUBPIXEL_EQUIANGULAR 1
+size_t ctd_xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, int block_size, int per_frame_pattern);
+int ctd_xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                              float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int mode,
+                              void* workspace, size_t workspace_bytes, int device, void* stream);
+int ctd_costvol_subpixel_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
+                             float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int type,
+                             float eps, int mode, int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
