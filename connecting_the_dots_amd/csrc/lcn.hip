@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kLcnTW* kLcnRows) void lcn_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Tolerance-level variant (`algo = 'fast'`, radius 1 .. 7): the same tile, the box sums in F32 as sliding windows -- the first
+// Tolerance-level variant (`algo = 'fast'`, radius 7; see lcn_fast_f32): the same tile, the box sums in F32 as sliding windows -- the first
 // output of a run is a fresh 11-term sum, each next one adds the entering and subtracts the leaving tap (3 additions per
 // output and pass instead of 11 half-rate f64 ones), runs of 8 columns / 4 rows.  The contract for the LCN is a tolerance
 // (ATen's conv2d summation order is unspecified): every output within 1e-5 |b| + 1e-6 of the reference's
@@ -168,7 +168,9 @@ __global__ __launch_bounds__(256) void lcn_fast_kernel(const float* __restrict__
   // sliding sums from radius 4 on; below, a window is at most 7 taps a side -- a fresh sum costs no more, and the residue a
   // bright sample leaves in a running sum (one ulp of ITS square) is divided by only 9 .. 49 taps: 3.5e-6 of std on the
   // variance floor at radius 1 (tools/fuzz_lcn.py)
-  constexpr bool SLIDE = R >= 4;
+  // (fresh sums at every radius since the float64 tests: a sliding run that drops a bright level keeps its rounding and
+  // a dark window after it, on the variance floor, carried 3.5 x the rule's bound at radius 7; only radius 7 runs here)
+  constexpr bool SLIDE = false;
   __shared__ float rs1[TRr][TW], rs2[TRr][TW];                     // row sums of x and x^2
   __shared__ float tile[TRr][TCc];                                 // reflect-padded input
   const int tid = threadIdx.x;
@@ -194,7 +196,8 @@ __global__ __launch_bounds__(256) void lcn_fast_kernel(const float* __restrict__
   // Everything below works on x - c: (x - avg) / std and std do not change under a shift, and E[x^2] - avg^2 of the shifted
   // samples no longer cancels against the image's DC level (frames with an offset of 10 and a deviation of 3 lose a factor
   // 12 of the f32 sums' accuracy otherwise: the reference golden "n").  c = 0 when the staged tile reaches zero (the plain
-  // sums: EXACT on a zero background with sparse bright samples), else the tile's MEAN (one reduction): close to every
+  // sums: EXACT on a zero background with sparse bright samples), else the tile's MEAN (one reduction; where it keeps c
+  // between 0 and every sample, see below): close to every
   // window's own mean wherever the tile has one level, and a sparse bright sample moves it by 1 / 1924 of its height.
   // (Until round 5 c was the tile's centre SAMPLE: a bright dot there on a dark flat background made every window of the
   // tile cancel against 0.81 -- std off by up to 2.5e-3 relative.  Tried on the way: the tile's value closest to zero,
@@ -221,7 +224,13 @@ __global__ __launch_bounds__(256) void lcn_fast_kernel(const float* __restrict__
   const float t_min = fminf(fminf(red[1][0], red[1][1]), fminf(red[1][2], red[1][3]));
   const float t_max = fmaxf(fmaxf(red[2][0], red[2][1]), fmaxf(red[2][2], red[2][3]));
   const float t_mean = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * (1.f / (float)(TRr * TCc));
-  const float ctr = (t_min <= 0.f && t_max >= 0.f) ? 0.f : t_mean;
+  // c lies between 0 and every sample of the tile (|x - c| <= |x|), so the f32 sums are never worse conditioned than the
+  // plain ones: the mean only where every sample is within a factor 2 of it, else the sample closest to zero.  (The mean
+  // alone: a dark window in a tile with bright rows cancelled against the bright level -- std up to 12 x the bound of
+  // tests/test_lcn_f64_gpu.py.)
+  const float ctr = (t_min <= 0.f && t_max >= 0.f) ? 0.f
+                    : t_min > 0.f ? (t_min >= 0.5f * t_mean ? t_mean : t_min)
+                                  : (t_max <= 0.5f * t_mean ? t_mean : t_max);
   // horizontal pass: item = (staged row, run of kLcnHC output columns)
   constexpr int CH = TW / kLcnHC, NT = kLcnHC + 2 * R;
   for (int it = tid; it < TRr * CH; it += 256) {
@@ -308,17 +317,15 @@ __global__ __launch_bounds__(256) void lcn_fast_kernel(const float* __restrict__
 #endif
 
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream) {
-  // radius 5 is the one the reference uses (exp_synph.py:41) and the one the tile shape was tuned for; 1 .. 7 share the kernel
+  // radius 7 only: with the tile-mean centring radii 1 .. 6 failed the float64 rule of tests/test_lcn_f64_gpu.py (a dark
+  // window in a tile with bright rows cancels against the bright level: std up to 12 x the bound at radii 1 .. 5; flat
+  // quantised levels 1.28 x the stock-f32 error at radius 6), so those radii are CTD_ERR_UNSUPPORTED (callers run
+  // lcn_f32).  The centring above cures the first, but at radius 5 it loses the accuracy the reference golden "n" (a
+  // level of 10 with samples down to 0.5) asks of 'fast' (tests/test_lcn_gpu.py)
   constexpr int TW = CTD_LCN_FAST_TW, TH = CTD_LCN_FAST_TH;
   dim3 grid(ceil_div(W, TW), ceil_div(H, TH), N), block(256);
-  switch (radius) {
-#define CTD_LCN_FAST_CASE(R) \
-    case R: hipLaunchKernelGGL((lcn_fast_kernel<R, TW, TH>), grid, block, 0, stream, x, y, stds, H, W, eps); break;
-    CTD_LCN_FAST_CASE(1) CTD_LCN_FAST_CASE(2) CTD_LCN_FAST_CASE(3) CTD_LCN_FAST_CASE(4)
-    CTD_LCN_FAST_CASE(5) CTD_LCN_FAST_CASE(6) CTD_LCN_FAST_CASE(7)
-#undef CTD_LCN_FAST_CASE
-    default: return CTD_ERR_UNSUPPORTED;
-  }
+  if (radius != 7) return CTD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((lcn_fast_kernel<7, TW, TH>), grid, block, 0, stream, x, y, stds, H, W, eps);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }

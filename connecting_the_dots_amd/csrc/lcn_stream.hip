@@ -11,17 +11,23 @@
 // kLsPF rows ahead) and is the only one that ever waits for a load: on gfx950 loads and stores retire in order on one
 // counter, so a wavefront that did both would wait for its newest stores every row (the same split as the volume
 // kernels of ncc_fast.hip); the three meet at one s_barrier per row.
-//   raw row u  --vertical 11-row sums V (sliding, per column)-->  horizontal 11-column sums (DPP wave shifts)
+//   raw row u  --vertical 11-row sums V (per column)-->  horizontal 11-column sums (DPP wave shifts)
 //              --> y = (x - avg) / std of row u - 5 --> stored (LCN output + the matcher's padded copy)
 //              --> vertical 9-row sums of y, y^2 as 3 + 3 + 3 (no running sum: every window is a fresh <= 4-level sum)
 //              --> horizontal 9-column sums (DPP) --> mean / reciprocal-deviation planes of row u - 9, listing rule.
 // Of a strip's 64 lanes the outer three each side are halo (5 + 4 columns, rounded to whole lanes): 232 valid columns.
 //
-// Numerics.  ACC = double ("exact"): the LCN box sums are formed in f64 -- exact, whatever the order, unless one
-// window spans more than 2^29 in magnitude -- and rounded once; the elementwise tail is the reference's f32 operation
-// order: the same bits as lcn_kernel / the oracle.  ACC = float ("fast"): f32 sums of samples centred by one constant
-// per wavefront, v_rcp / v_sqrt in the tail: tolerance level, and only where E[(x - c)^2] is not large against the
-// window's variance (see DESIGN: an f32 one-pass variance cannot be better than that).
+// Numerics.  ACC = double ("exact"): the LCN box sums are formed in f64 -- a fresh 11-row sum per row and column from
+// the raw ring, then the 11-column tree -- and rounded once; the elementwise tail is the reference's f32 operation order.
+// f64 sums of f32 samples are exact in any order where hi - lo <= 53 (hi = ceil(log2 sum |v|) over the window, lo = the
+// lowest set bit of its nonzero samples; separately for x and for the f32 x*x): there these are the bits of lcn_kernel /
+// the oracle (tests/test_lcn_f64_gpu.py); and a rounding never outlives the window it was made in.  ACC = float
+// ("fast"): f32 sums of samples centred by one constant per wavefront, v_rcp / v_sqrt in the tail: tolerance level, and
+// only where E[(x - c)^2] is not large against the window's variance (see DESIGN: an f32 one-pass variance cannot be
+// better than that) and no level much brighter than the window has slid out of the band's sums before it: a band that
+// starts bright and runs into a dark level keeps the bright sums' roundings (include/ctd_hip.h states the condition).
+// Keeping c between 0 and every fed sample and restarting the sums after such a drop met the f64 rule there, but made
+// this kernel 29.7 -> 43.8 us at config 2.
 // The pre-pass statistics follow ncc_prepass_kernel<9, true> (f32 sums of the LCN output, which is centred by
 // construction: the image constant is 0 here) with the same listing rule.
 #include <cstdlib>
@@ -198,7 +204,7 @@ __global__ __launch_bounds__(192) void lcn_prepass_stream_kernel(LcnStreamArgs a
       }
       return v;
     };
-    ACC V1[4], V2[4];                                            // sums over the 11 newest raw rows, per column
+    ACC V1[4], V2[4];                                            // sums over the 11 newest raw rows, per column (fast: sliding)
 #pragma unroll
     for (int i = 0; i < 4; ++i) V1[i] = V2[i] = (ACC)0;
     // fast variant: samples centred by one constant per wavefront, the in-image value of the first row closest to zero:
@@ -222,12 +228,14 @@ __global__ __launch_bounds__(192) void lcn_prepass_stream_kernel(LcnStreamArgs a
         }
         cen = __builtin_amdgcn_fmed3f(0.f, mn, mx);
       }
+      if constexpr (!EXACT) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float vn = EXACT ? xn[i] : xn[i] - cen;
-        const float qn = vn * vn;                                // data**2 is an f32 tensor (networks.py:528)
-        V1[i] += (ACC)vn;
-        V2[i] += (ACC)qn;
+        for (int i = 0; i < 4; ++i) {
+          const float vn = xn[i] - cen;
+          const float qn = vn * vn;                              // data**2 is an f32 tensor (networks.py:528)
+          V1[i] += vn;
+          V2[i] += qn;
+        }
       }
     }
     // byte offsets of the lane's quad inside this frame's tensors / planes (32 bits: lcn_stream_supported; unsigned
@@ -242,6 +250,23 @@ __global__ __launch_bounds__(192) void lcn_prepass_stream_kernel(LcnStreamArgs a
       // ---- LCN of row cur = ry_first + k - 10 (its own sample: the feed 5 steps ago)
       const int cur = ry_first + k - (NR - 1);
       const ls_f32x4 xc = *(const ls_f32x4*)&xring[(k - kLsR) & (kLsXRing - 1)][4 * lane];
+      if constexpr (EXACT) {
+        // a fresh 11-row sum per row, from the ring (feeds k - 10 .. k, ascending): no rounding outlives its window.
+        // (A sliding sum V = (V + new) - old keeps the rounding of a sample that entered next to large ones after both
+        // have left, and a later window whose own sum is exact then rounds differently: tests/lcn_traps.py.)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) V1[i] = V2[i] = 0.0;
+#pragma unroll
+        for (int j = NR - 1; j >= 0; --j) {
+          const ls_f32x4 xr = *(const ls_f32x4*)&xring[(k - j) & (kLsXRing - 1)][4 * lane];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float qr = xr[i] * xr[i];                      // data**2 is an f32 tensor (networks.py:528)
+            V1[i] += (double)xr[i];
+            V2[i] += (double)qr;
+          }
+        }
+      }
       ACC S1[4], S2[4];
       ls_hsum11(V1, S1);
       ls_hsum11(V2, S2);
@@ -289,14 +314,16 @@ __global__ __launch_bounds__(192) void lcn_prepass_stream_kernel(LcnStreamArgs a
       wg_barrier();                                              // feed k has landed (k == n_raw: the last hand-over)
       if (k == n_raw) break;
       // ---- next raw row: add it, drop the row that leaves the window (the feed 11 steps ago)
-      const ls_f32x4 xn = raw_row(k);
-      const ls_f32x4 xo = *(const ls_f32x4*)&xring[(k - NR) & (kLsXRing - 1)][4 * lane];
+      const ls_f32x4 xn = raw_row(k);                         // (exact: only the border rule, the sums are fresh)
+      if constexpr (!EXACT) {
+        const ls_f32x4 xo = *(const ls_f32x4*)&xring[(k - NR) & (kLsXRing - 1)][4 * lane];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float vn = EXACT ? xn[i] : xn[i] - cen, vo = EXACT ? xo[i] : xo[i] - cen;
-        const float qn = vn * vn, qo = vo * vo;
-        V1[i] = (V1[i] + (ACC)vn) - (ACC)vo;
-        V2[i] = (V2[i] + (ACC)qn) - (ACC)qo;
+        for (int i = 0; i < 4; ++i) {
+          const float vn = xn[i] - cen, vo = xo[i] - cen;
+          const float qn = vn * vn, qo = vo * vo;
+          V1[i] = (V1[i] + vn) - vo;
+          V2[i] = (V2[i] + qn) - qo;
+        }
       }
     }
     return;

@@ -355,9 +355,9 @@ def lcn(data, radius, epsilon, algo=None):
     """data [N,1,H,W] f32 -> ((data - avg) / std, std), std = sqrt(E[x^2] - avg^2 + 1e-6) + epsilon,
     box statistics over a (2*radius+1)^2 reflect-padded window.  Not differentiable (the reference
     only ever applies it to input images, exp_synph.py:84-91).
-    algo (additive): 'exact' (default: f64 box sums, bit-identical to the oracle) | 'fast' (radius 1 .. 7, other radii run 'exact': f32 sliding sums of
-    tile-centred samples, within 1e-5 |b| + 1e-6 of 'exact' and of the reference -- whose own summation order is unspecified --
-    except on the variance floor of flat non-zero levels, see include/ctd_hip.h)."""
+    algo (additive): 'exact' (default: f64 box sums, bit-identical to the oracle) | 'fast' (radius 7: f32 sliding sums of
+    tile-centred samples, within 1e-6 |b| + 1e-6 + 64 u kappa of the float64 reference and at most 1.25 x the stock-f32
+    error plus a floor, the rule of tests/test_lcn_f64_gpu.py; every other radius runs 'exact', see include/ctd_hip.h)."""
     _check(data, "data", (torch.float32,))
     if data.dim() != 4 or data.shape[1] != 1:
         raise RuntimeError("lcn expects [N,1,H,W]")
@@ -370,7 +370,7 @@ def lcn(data, radius, epsilon, algo=None):
     algo = algo or "exact"
     if algo not in ("exact", "fast"):
         raise RuntimeError("unknown algo %r" % (algo,))
-    fn = _lib.lib().ctd_lcn_fast_f32 if (algo == "fast" and 1 <= int(radius) <= 7) else _lib.lib().ctd_lcn_f32
+    fn = _lib.lib().ctd_lcn_fast_f32 if (algo == "fast" and int(radius) == 7) else _lib.lib().ctd_lcn_f32
     st = fn(_ptr(data), _ptr(y), _ptr(std), N, H, W, int(radius), float(epsilon), dev.index, _stream(dev))
     _lib.check(st, "lcn")
     return y, std
@@ -382,8 +382,11 @@ def lcn_xcorrvol_argmax(raw, in1, n_disps, block_size, radius=5, epsilon=0.05, r
     as ONE call whose first kernel streams the raw frames once and leaves both the LCN outputs and the matcher's window
     statistics (ctd_lcn_xcorrvol_argmax_f32).  raw [N,1,H,W]; in1 [1,H,W] | [N,1,H,W].
     Returns (lcn, std, idx, best[, volume]).  lcn_algo 'exact': lcn / std carry the bits of `lcn(..., algo='exact')`;
-    'fast': f32 box sums, tolerance level on well-conditioned windows only (see include/ctd_hip.h).
-    Shapes the fused kernel does not cover run the two calls it replaces.
+    'fast': f32 box sums, within 1e-6 |b| + 4e-6 + 64 u kappa of the float64 LCN (the rule of
+    tests/test_lcn_f64_gpu.py) on frames without long runs of a dark level next to a bright one -- there use 'exact'
+    (see include/ctd_hip.h).
+    Shapes the fused kernel does not cover, and rerank_eps < 0 with return_volume=True (a plain argmax of the fast
+    scores, as `xcorrvol_argmax` defines it), run the two calls it replaces.
     subpixel: None (default) | "parabola" | "equiangular": also return (disp, refined) of
     `xcorrvol_subpixel(lcn, in1, idx, ...)` -- against the LCN output this call returns -- at the end of the tuple."""
     if subpixel is not None:
@@ -405,7 +408,9 @@ def lcn_xcorrvol_argmax(raw, in1, n_disps, block_size, radius=5, epsilon=0.05, r
     D, bs = int(n_disps), int(block_size)
     if not (0 <= int(radius) < min(H, W)):
         raise RuntimeError("lcn: radius must be smaller than the image (ReflectionPad2d rule)")
-    if not L.ctd_lcn_xcorrvol_supported(H, W, D, int(radius), bs):
+    # rerank_eps < 0 with a volume means a plain argmax of the fast scores (xcorrvol_argmax); the fused kernel always
+    # ranks with eps >= 0, so that call runs as the two calls it replaces, as on the shapes the fused kernel does not cover
+    if not L.ctd_lcn_xcorrvol_supported(H, W, D, int(radius), bs) or (float(rerank_eps) < 0 and return_volume):
         y, std = lcn(raw, radius, epsilon, algo=lcn_algo)
         out = xcorrvol_argmax(y, in1, D, bs, return_volume=return_volume, algo="fast", rerank_eps=rerank_eps, prepared=prepared)
         return (y, std) + tuple(out)

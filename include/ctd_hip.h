@@ -259,16 +259,17 @@ int ctd_costvol_subpixel_f32(const float* im, const float* pattern, long pattern
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
  * model/networks.py:507-533 (ReflectionPad2d + two all-ones Conv2d + 6 elementwise ops).
  *   x [N][1][H][W] -> y = (x-avg)/std, std  (both [N][1][H][W]);  radius < min(H, W)
+ * Box sums in f64 in the order of the CPU oracle (rows, then columns, ascending), rounded once, and the reference's f32
+ * tail: the oracle's bits at every pixel (tests/test_lcn_f64_gpu.py, trap and high-dynamic-range frames included).
  * -------------------------------------------------------------------------------------- */
 int ctd_lcn_f32(const float* x, float* y, float* std_out, int N, int H, int W, int radius,
                 float eps, int device, void* stream);
-/* tolerance-level variant (radius 1 .. 7, else CTD_ERR_UNSUPPORTED): f32 sliding-window box sums instead of f64 ones, of
- * samples centred per 64 x 16 tile (0 where the tile reaches zero, else the tile's mean).  Every output within
- * 1e-5 |b| + 1e-6 of ctd_lcn_f32 and of the reference's networks.LCN (whose conv2d summation order is unspecified) where a
- * window's variance is not small against its mean square about that centre -- uniform / textured frames, frames with a DC
- * level, dots on a zero background; windows of a low-noise non-zero level with no sample in them sit on the 1e-6 variance
- * floor, where ANY f32 one-pass variance (the reference's included) is good to E[(x - c)^2] * 2^-24 per rounding: up to
- * 3e-6 absolute of std there (tools/fuzz_lcn.py). */
+/* tolerance-level variant, radius 7 only (CTD_ERR_UNSUPPORTED otherwise: at radii 1 .. 6 it failed the float64 rule
+ * below, on frames with dark and bright rows and on flat quantised levels; call ctd_lcn_f32): f32 sliding-window box
+ * sums of samples centred per 64 x 16 tile by a constant between 0 and every sample of the tile (0 where the tile
+ * reaches zero, its mean where every sample is within a factor 2 of it, else the sample closest to zero).  Every output within
+ * 1e-6 |b| + 1e-6 + 64 u kappa of the float64 LCN (u = 2^-24, kappa from the window's f64 E[x^2], var and std: the rule
+ * of tests/test_lcn_f64_gpu.py), with its largest error at most 1.25 x the stock-torch f32 error plus that floor. */
 int ctd_lcn_fast_f32(const float* x, float* y, float* std_out, int N, int H, int W, int radius,
                      float eps, int device, void* stream);
 
@@ -282,11 +283,19 @@ int ctd_lcn_fast_f32(const float* x, float* y, float* std_out, int N, int H, int
  *   raw [frames][1][H][W] -> lcn_out, std_out [frames][1][H][W] (both required);  in1 = the LCN'd pattern, as for
  *   ctd_xcorrvol_argmax_f32, whose remaining arguments, outputs, workspace and CTD_PATTERN_PREPARED rule apply unchanged
  *   (algo = CTD_NCC_FAST [| CTD_PATTERN_PREPARED]).
- * lcn_algo: CTD_LCN_EXACT -- f64 box sums and the reference's f32 elementwise tail: lcn_out / std_out carry the bits of
- *   ctd_lcn_f32 (f64 sums of f32 samples are exact in any order unless one window spans more than 2^29 in magnitude);
- *   CTD_LCN_FAST -- f32 sums of samples centred by one constant per wavefront, v_rcp / v_sqrt tail: tolerance level,
- *   and only for windows whose variance is not small against their mean square (an f32 one-pass variance cannot do
- *   better: E[x^2] - avg^2 cancels; the reference's own f32 conv2d has the same limit).
+ * lcn_algo: CTD_LCN_EXACT -- f64 box sums (a fresh 11-row sum per row) and the reference's f32 elementwise tail:
+ *   lcn_out / std_out carry the bits of ctd_lcn_f32 wherever a window's f64 sums are exact in any order, that is where
+ *   hi - lo <= 53 with hi = ceil(log2 sum |v|) over the window and lo the lowest set bit of its nonzero samples, for the
+ *   samples and for their f32 squares alike; no rounding outlives the window it was made in;
+ *   CTD_LCN_FAST -- f32 sums of samples centred by one constant per wavefront (the in-image sample nearest zero of the
+ *   first row a band reads), sliding over the band's rows, v_rcp / v_sqrt tail: within 1e-6 |b| + 4e-6 + 64 u kappa of
+ *   the float64 LCN (the rule of tests/test_lcn_f64_gpu.py; the 4e-6 is an estimate of the rounding a bright sample of
+ *   magnitude up to 1 leaves in a band's sliding sums, tested at bands of up to 64 rows), and at most 1.25 x the
+ *   stock-torch f32 error plus that floor -- on frames without long runs of a dark level next to a bright one: a dark
+ *   window below a bright first row cancels against that centre, and one after a bright level has slid out of the sums
+ *   keeps its roundings (std 7.6 x that bound, 3.3 x the stock-f32 error, on rows of 0.02 under rows of 0.7 .. 1).  Use CTD_LCN_EXACT there.
+ * rerank_eps < 0 ranks with eps = 0 here: there is no plain argmax of the fast scores (a caller that wants one with a
+ *   volume calls ctd_lcn_f32 + ctd_xcorrvol_argmax_f32, as the Python wrapper does).
  * Supported where ctd_lcn_xcorrvol_supported() says so (radius 5, block 9, W % 4 == 0, W >= 16, H >= 11 and the ranked
  * fast path of ctd_xcorrvol_rank_supported()); CTD_ERR_UNSUPPORTED otherwise (call ctd_lcn_f32 + ctd_xcorrvol_argmax_f32).
  * -------------------------------------------------------------------------------------- */

@@ -1,4 +1,4 @@
-"""Stock-torch restatements of the training losses (model/networks.py of the reference), for the float64 gradient
+"""Stock-torch restatements of the training losses and of LCN (model/networks.py of the reference), for the float64
 tests.  Not a conftest: a plain helper module that tests import.
 
 Every reference takes the f32 tensors the HIP kernels take, promotes them to `dtype` (float64 by default; float32 gives
@@ -185,3 +185,22 @@ def pattern_loss(disp, im, pattern, mask, type, eps=0.5, grad_proj=None, dtype=t
             pairs.append(pair.detach().abs() <= c * (vw + vb) + fl)
     return Ref((num / den, torch.cat(projs)), {"disp": torch.cat(grads)},
                {"ix": torch.cat(ixs), "iy": torch.cat(iys), "gproj": torch.cat(gprojs), ("pair" if pair_tol is None else "pair_near"): torch.cat(pairs)})
+
+
+def lcn(x, radius, eps, dtype=torch.float64):
+    """LCN.tforward (networks.py:507-533): ReflectionPad2d(radius), two all-ones (2r+1)^2 conv2d (of x and of x**2),
+    avg = box / n, std = sqrt(box(x**2) / n - avg**2 + 1e-6) + eps, y = (x - avg) / std.  x [N,1,H,W] (any float
+    dtype, promoted to `dtype`; float32 is the stock-torch f32 yardstick).  Returns a Ref: value (y, std), no grads, inter 'avg',
+    'ex2' (box(x**2) / n), 'var' (ex2 - avg**2 + 1e-6, the argument of the square root).  x**2 is squared in `dtype`:
+    at float64 it is exact for f32 samples, so it equals the square of the f32 tensor the module squares, to within
+    that tensor's one rounding (at most 2^-24 relative, which the tests' tolerance covers)."""
+    d = x.detach().to(dtype)
+    n = float((2 * radius + 1) ** 2)
+    k = torch.ones(1, 1, 2 * radius + 1, 2 * radius + 1, dtype=dtype, device=d.device)
+    pad = torch.nn.ReflectionPad2d(radius)
+    box = F.conv2d(pad(d), k)
+    avg = box / n
+    ex2 = F.conv2d(pad(d ** 2), k) / n
+    var = ex2 - avg ** 2 + 1e-6
+    std = torch.sqrt(var) + eps
+    return Ref(((d - avg) / std, std), {}, {"avg": avg, "ex2": ex2, "var": var})

@@ -134,3 +134,30 @@ def test_block_loss_ref_matches_package_composition():
         got, pair = R.block_loss(es, ta, 9, name, 0.5)
         assert torch.allclose(got, photometric_loss_pytorch(es, ta, 9, name, 0.5), rtol=1e-12, atol=1e-15), name
         assert pair.shape == (2, 81, 13, 21)
+
+
+def test_lcn_ref_vs_reference_golden():
+    """the LCN vectors captured from networks.LCN, at the tolerances tests/test_oracle_golden.py holds the oracle to"""
+    g = golden("lcn_networks")
+    for key, r, eps in (("0", 5, 0.05), ("1", 5, 0.05), ("r2", 2, 0.1)):
+        ref = R.lcn(t(g["x_" + key]), r, eps)
+        y, s = ref.value
+        assert y.dtype == torch.float64
+        assert_close(s.numpy(), g["std_" + key], what="std " + key)
+        assert_close(y.numpy(), g["y_" + key], rtol=2e-5, atol=2e-6, what="lcn " + key)
+        assert torch.allclose(ref.inter["var"], ref.inter["ex2"] - ref.inter["avg"] ** 2 + 1e-6, rtol=0, atol=0)
+        f32 = R.lcn(t(g["x_" + key]), r, eps, dtype=torch.float32)
+        assert f32.value[0].dtype == torch.float32
+        assert_close(f32.value[1].numpy(), g["std_" + key], what="f32 std " + key)
+
+
+@pytest.mark.parametrize("radius", [0, 1, 5, 9])
+def test_lcn_ref_vs_oracle(oracle, radius):
+    """the f64 reference against the oracle (f64 sums, f32 tail) on frames with a DC level, and at radius = min(H, W) - 1"""
+    rs = np.random.RandomState(radius)
+    for x in ((rs.rand(2, 1, 24, 37) * 3 + rs.randn(2, 1, 1, 1)).astype(np.float32),
+              rs.rand(1, 1, radius + 1, 30).astype(np.float32), rs.rand(1, 1, 30, radius + 1).astype(np.float32)):
+        y0, s0 = oracle.lcn(x, radius, 0.05)
+        y, s = R.lcn(t(x), radius, 0.05).value
+        assert_close(s.numpy(), s0, what="std r%d" % radius)
+        assert_close(y.numpy(), y0, rtol=2e-5, atol=2e-6, what="lcn r%d" % radius)

@@ -44,7 +44,8 @@ def test_lcn_bit_exact_vs_oracle(te, oracle, shape):
 
 @pytest.mark.parametrize("shape", [(2, 24, 32), (1, 40, 53), (1, 432, 512), (2, 33, 65), (1, 31, 31), (3, 97, 34), (1, 11, 300)])
 def test_lcn_fast_within_tolerance(te, oracle, shape):
-    """algo='fast' (f32 sliding box sums, radius 5): every output within 1e-5 |b| + 1e-6 of the oracle, on uniform frames,
+    """algo='fast' at radius 5 (which runs the f64 kernel since the f32 one serves radius 7 only): every output within
+    1e-5 |b| + 1e-6 of the oracle, on uniform frames,
     frames with a per-frame DC offset, binary patterns, structured-light frames (flat or low-noise dark background with
     sparse bright samples, one of them at every tile's centre -- the case the round-4 centring failed on) and the
     reference's own goldens (the contract for the LCN is a tolerance: ATen's conv2d summation order is unspecified)"""
@@ -68,7 +69,7 @@ def test_lcn_fast_vs_reference_golden(te):
         y, s = te.lcn(dev(g["x_%d" % k]), 5, 0.05, algo="fast")
         assert_close(s.cpu().numpy(), g["std_%d" % k], what="std %d" % k)
         assert_close(y.cpu().numpy(), g["y_%d" % k], rtol=2e-5, atol=2e-6, what="lcn %d" % k)
-    # the other radii the f32 kernel serves (1 .. 7)
+    # another radius of algo='fast' (the exact kernel since the f32 one serves radius 7 only)
     y, s = te.LCN(2, 0.1, algo="fast")(dev(g["x_r2"]))
     assert_close(s.cpu().numpy(), g["std_r2"], what="std r2")
     assert_close(y.cpu().numpy(), g["y_r2"], rtol=2e-5, atol=2e-6, what="lcn r2")
@@ -76,7 +77,7 @@ def test_lcn_fast_vs_reference_golden(te):
 
 @pytest.mark.parametrize("radius", [1, 3, 4, 6, 7, 9])
 def test_lcn_fast_other_radii(te, oracle, radius):
-    """algo='fast' for the radii 1 .. 7 (same kernel, tap loops of another length) against the oracle; 9 runs the f64 kernel"""
+    """algo='fast' for other radii against the oracle: 7 runs the f32 kernel, the others the f64 one"""
     rs = np.random.RandomState(radius)
     x = (rs.rand(2, 1, 45, 150) * 3 + rs.randn(2, 1, 1, 1)).astype(np.float32)
     y0, s0 = oracle.lcn(x, radius, 0.05)
