@@ -75,6 +75,10 @@ SIGNATURES = {
     "ctd_render_mesh_proj_f32": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp,
                                           _c_float, _c_float, _vp, _vp, _vp, _c_int, _vp]),
     "ctd_render_mesh_f32": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "ctd_syn_finish_f32": (_c_int, [_vp] * 4 + [ctypes.c_double, _c_float, _c_int, _c_float, _c_int] + [_vp] * 5 +
+                           [_c_int] * 3 + [_c_int, _vp]),
+    "ctd_augment_f32": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp] + [_c_int] * 3 + [_c_int, _vp]),
+    "ctd_salt_pepper_f32": (_c_int, [_vp] * 5 + [_c_int] * 4 + [_c_int, _vp]),
     "ctd_nn_f32": (_c_int, [_vp, _vp, _c_long, _c_long, _vp, _c_int, _vp]),
     "ctd_nn_f64": (_c_int, [_vp, _vp, _c_long, _c_long, _vp, _c_int, _vp]),
     "ctd_crosscheck": (_c_int, [_vp, _vp, _c_long, _c_long, _vp, _c_int, _vp]),

@@ -646,4 +646,42 @@ int ctd_render_mesh_f32(const float* verts, const float* colors, const float* no
                          (hipStream_t)stream);
 }
 
+
+static bool syn_shape_ok(int N, int H, int W) {
+  return N >= 0 && N <= 65535 && H > 0 && W > 0 && (double)H * W * 3 < 2147483648.0;
+}
+
+int ctd_syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend,
+                       double baseline_focal, float grad_threshold, int lcn_radius, float lcn_eps, int lcn_clip,
+                       float* im, float* ambient, float* grad, float* disp, float* mask, int N, int H, int W, int device,
+                       void* stream) {
+  if (!syn_shape_ok(N, H, W) || lcn_radius < 0) return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!depth || !color || !normal || !blend || !im || !ambient || !grad) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return syn_finish_f32(depth, color, normal, blend, baseline_focal, grad_threshold, lcn_radius, lcn_eps, lcn_clip, im,
+                        ambient, grad, disp, mask, N, H, W, (hipStream_t)stream);
+}
+
+int ctd_augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
+                    uint32_t* minmax, int N, int H, int W, int device, void* stream) {
+  if (!syn_shape_ok(N, H, W) || (noise_f64 != 0 && noise_f64 != 1)) return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!img || !params || !out || !minmax) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return augment_f32(img, noise, noise_f64, params, out, minmax, N, H, W, (hipStream_t)stream);
+}
+
+int ctd_salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
+                        const int64_t* pepper, int kmax, int N, int H, int W, int device, void* stream) {
+  if (!syn_shape_ok(N, H, W) || kmax < 0) return CTD_ERR_INVALID_ARG;
+  if (N == 0 || kmax == 0) return CTD_OK;
+  if (!img || !minmax || !counts || !salt || !pepper) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return salt_pepper_f32(img, minmax, counts, salt, pepper, kmax, N, H, W, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -176,4 +176,14 @@ int render_mesh_f32(const float* verts, const float* colors, const float* normal
                     const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth, float* color, float* normal,
                     hipStream_t stream);
 
+
+// synth.hip
+int syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend, double bf,
+                   float thr, int ks, float eps, int clip, float* im, float* amb, float* grad, float* disp, float* mask,
+                   int N, int H, int W, hipStream_t stream);
+int augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
+                uint32_t* minmax, int N, int H, int W, hipStream_t stream);
+int salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
+                    const int64_t* pepper, int kmax, int N, int H, int W, hipStream_t stream);
+
 }  // namespace ctd

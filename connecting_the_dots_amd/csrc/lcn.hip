@@ -13,6 +13,7 @@
 // The CPU oracle (oracle/ctd_oracle.c: ctd_oracle_lcn_f32) uses the same order, so the
 // two agree bit for bit.
 #include "ctd_internal.h"
+#include "ctd_lcn_window.h"
 
 namespace ctd {
 
@@ -379,18 +380,7 @@ __global__ __launch_bounds__(256) void lcn_datagen_kernel(const float* __restric
     float o = 0.f, sd = 0.f;
     if (y >= ks && y < H - ks && x >= ks && x < W - ks) {
       const float* win = lds_f + ty * TC + tx;                       // top-left tap of the window
-      float mean = 0.f;
-      for (int i = 0; i <= 2 * ks; ++i)
-        for (int j = 0; j <= 2 * ks; ++j) mean += win[i * TC + j];
-      mean = mean / num;
-      float acc = 0.f;
-      for (int i = 0; i <= 2 * ks; ++i)
-        for (int j = 0; j <= 2 * ks; ++j) {
-          const float d = win[i * TC + j] - mean;
-          acc = acc + d * d;
-        }
-      sd = sqrtf(acc / num);
-      o = (win[ks * TC + ks] - mean) / (sd + eps);
+      o = lcn_datagen_window(win, TC, ks, num, eps, &sd);
     }
     out[base + (long)y * W + x] = o;
     out_std[base + (long)y * W + x] = sd;

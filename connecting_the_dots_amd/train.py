@@ -126,7 +126,10 @@ class TrackTrainer:
 
     A batch is a dict of device tensors shaped like the reference's after `copy_data` (exp_synphge.py:93-115):
         im{s}   [tl, B, 1, H_s, W_s]  raw IR frames of scale s = 0..3 (H_s = H / 2^s)
-        grad{s} [tl, B, 1, H_s, W_s]  gradient magnitude of the ground-truth disparity, scales 0..2 (edge supervision)
+        grad{s} [tl, B, 1, H_s, W_s]  edge target of scales 0..2 (edge supervision): the gradient magnitude of the
+                                      ground-truth disparity (tests/workloads.track_batch), or the reference's own
+                                      target, the LCN of the ambient image's Sobel magnitude (synth.finish_render /
+                                      synth.render_track_sample)
         id      [B]                   sample ids; the edge decoder is supervised where id > train_edge
         R [tl, B, 3, 3], t [tl, B, 3] camera poses of the track frames
     Terms, in the reference's order (exp_synphge.py:141-200): photometric pattern similarity of every scale (all four

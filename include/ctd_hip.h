@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -470,6 +470,65 @@ int ctd_render_mesh_f32(const float* verts, const float* colors, const float* no
                         const int* faces, int n_faces, const float* cam, int cam_width, int cam_height,
                         const float* shader, float* depth, float* color, float* normal, int device,
                         void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * Training-sample finishing of the synthetic data path (additive in ABI version 5).
+ *
+ * ctd_syn_finish_f32: data/create_syn_data.py:163-188 for N rendered frames of one size (the outputs of
+ * ctd_render_mesh_proj_f32; `normal` holds the shaded ambient image and must be zero where nothing was hit).
+ *   depth [N][H][W], color [N][H][W][3], normal [N][H][W][3], blend [N] (f64): device
+ *   im, ambient, grad [N][H][W] written; disp, mask [N][H][W] written unless NULL
+ * Operation order, all f32 without FMA (numpy 1.x value-based casting of the reference's f64 scalars):
+ *   im_c = ((c0 + c1) + c2) / 3.0f;  ambient = ((n0 + n1) + n2) / 3.0f             (np.mean(axis=2))
+ *   im   = (float)b * im_c + (float)(1.0 - b) * ambient                           (1 - b formed in double)
+ *   disp = (float)baseline_focal / depth  (inf where depth == 0, negative where the renderer left -1);
+ *   mask = depth > 0 ? 1 : 0
+ *   gx, gy = cv2.Sobel(ambient, CV_32F, 1,0 | 0,1, ksize=5), unnormalised: gx = derivative taps [-1,-2,0,2,1] along x,
+ *     smoothing taps [1,4,6,4,1] along y, gy the transpose; BORDER_REFLECT_101; separable, the row pass first, then
+ *     the column pass, each output of a pass s = 0, s += k[j] * v[j] for j = 0..4 in f32
+ *   pre  = fmaxf(sqrtf(gx*gx + gy*gy) - grad_threshold, 0)
+ *   grad = lcn_datagen(pre, lcn_radius, lcn_eps), clipped to [0, 1] when lcn_clip != 0: BIT-IDENTICAL to
+ *     ctd_lcn_datagen_f32 applied to `pre` (the same window code; the border of width lcn_radius is zero, all of the
+ *     output when H or W <= 2 * lcn_radius)
+ * Exact: every output is bit-identical to a numpy f32 evaluation in this order.  Assumed, not verified (cv2 is not
+ * part of the test environment): that OpenCV's float Sobel equals this order -- its SIMD row / column filters may
+ * group the symmetric taps differently, which moves |Sobel| by a few ulp; the bound against a float64 evaluation is
+ * what tests/test_synth_gpu.py checks.  CTD_ERR_UNSUPPORTED when the LDS tile of lcn_radius exceeds 64 KiB.
+ *
+ * ctd_augment_f32: data/commons.py:46-107 `augment_image` with max_shift = 0, blur + noise + clip; salt and pepper is
+ * the separate ctd_salt_pepper_f32 after it.  One parameter row per image, on the device:
+ *   blur != 0: 5x5 Gaussian blur, cv2.GaussianBlur(img, (5,5), sigma) on f32 with taps k[j] = (float)(e_j / sum(e)),
+ *     e_j = exp(-(j-2)^2 / (2 sigma^2)) (formed in double by the caller); BORDER_REFLECT_101; row pass then column
+ *     pass, s = 0, s += k[j] * v[j] in f32.  blur == 0: the image passes through untouched.
+ *   v = (double)blurred + (double)noise * noise_scale, clipped to [0, 1] in double, rounded to f32 once.  noise is
+ *     [N][H][W] f32 (noise_f64 = 0) or f64 (noise_f64 = 1: the reference's f64 noise term itself, bit for bit), or
+ *     NULL (no noise).
+ *   minmax [N][2] (u32, device): the min and max of the INPUT image as ordered keys, key(x) = bits(x) ^ (x < 0 ?
+ *     0xffffffff : 0x80000000); word 0 holds ~key(min), word 1 key(max).  The call zeroes them on `stream` first.
+ * Exact: bit-identical to a numpy evaluation in this order; with blur == 0 bit-identical to augment_image itself.
+ * Assumed, not verified: OpenCV builds the f32 Gaussian taps as e_j * (1 / sum(e)) in double (not e_j / sum(e)),
+ * which can differ in the last bit of the double and, rarely, of the f32 tap; and it may group the symmetric taps
+ * of its SIMD filters differently (a few ulp).  Against a float64 blur with exact taps the stated order is within its
+ * forward-error bound 14 * 2^-24 * blur(|x|) (tests/test_synth_gpu.py); 2 ulp of the result is NOT a bound of it.
+ *
+ * ctd_salt_pepper_f32: commons.py:96-101 on the output of ctd_augment_f32.  Per image n, counts[n] (clamped to
+ * [0, kmax]) indices into the flattened image from salt[n][0..] and pepper[n][0..] (int64 [N][kmax], drawn with
+ * replacement): writes clip(max) at the salt indices, then clip(min) at the pepper indices (pepper wins a shared
+ * index), min / max decoded from `minmax`.  Indices outside [0, H*W) are skipped.  No workspace.
+ * -------------------------------------------------------------------------------------- */
+typedef struct ctd_augment_params {
+  int32_t blur;                  /* 1: blur with taps[], 0: no blur                     */
+  float taps[5];                 /* Gaussian taps, f32                                   */
+  double noise_scale;            /* multiplies the noise plane, in double               */
+} ctd_augment_params;            /* 32 bytes, one per image                              */
+int ctd_syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend,
+                       double baseline_focal, float grad_threshold, int lcn_radius, float lcn_eps, int lcn_clip,
+                       float* im, float* ambient, float* grad, float* disp, float* mask, int N, int H, int W,
+                       int device, void* stream);
+int ctd_augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
+                    uint32_t* minmax, int N, int H, int W, int device, void* stream);
+int ctd_salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
+                        const int64_t* pepper, int kmax, int N, int H, int W, int device, void* stream);
 
 #ifdef __cplusplus
 }
