@@ -19,6 +19,14 @@ class PatternLevel(ctypes.Structure):
 
 _levels_p = ctypes.POINTER(PatternLevel)
 
+
+class HdTables(ctypes.Structure):
+    """ctd_hd_tables of include/ctd_hip.h (the packed HyperDepth forests of a row range)"""
+    _fields_ = [("nodes", _vp), ("roots", _vp), ("leaf_off", _vp), ("leaf_sum", _vp), ("entries", _vp),
+                ("n_nodes", ctypes.c_int64), ("n_leaves", ctypes.c_int64), ("n_entries", ctypes.c_int64),
+                ("row0", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_trees", ctypes.c_int32),
+                ("n_classes", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
 # name -> (restype, argtypes); mirrors include/ctd_hip.h one to one
 SIGNATURES = {
     "ctd_version": (_c_int, []),
@@ -84,6 +92,7 @@ SIGNATURES = {
     "ctd_crosscheck": (_c_int, [_vp, _vp, _c_long, _c_long, _vp, _c_int, _vp]),
     "ctd_proj_nn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_vp, _c_int, _vp]),
     "ctd_proj_nn_f64": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_vp, _c_int, _vp]),
+    "ctd_hyperdepth_eval_f32": (_c_int, [ctypes.POINTER(HdTables), _vp] + [_c_int] * 6 + [_vp, _c_int, _vp]),
 }
 
 # measurement hooks of include/ctd_hip_bench.h (bench.py, tools/): not part of the drop-in interface

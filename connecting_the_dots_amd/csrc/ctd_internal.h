@@ -186,4 +186,10 @@ int augment_f32(const float* img, const void* noise, int noise_f64, const ctd_au
 int salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
                     const int64_t* pepper, int kmax, int N, int H, int W, hipStream_t stream);
 
+// hyperdepth.hip
+size_t hyperdepth_lds_bytes(int n_trees, int n_classes);
+long hyperdepth_grid(int N, int H, int W);
+int hyperdepth_eval_f32(const ctd_hd_tables& tab, const uint8_t* ims, int N, int H, int W, int row_from, int row_to,
+                        int n_disp_bins, float* out, hipStream_t stream);
+
 }  // namespace ctd

@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -529,6 +529,56 @@ int ctd_augment_f32(const float* img, const void* noise, int noise_f64, const ct
                     uint32_t* minmax, int N, int H, int W, int device, void* stream);
 int ctd_salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
                         const int64_t* pepper, int kmax, int N, int H, int W, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * HyperDepth random-forest disparity evaluation (additive in ABI version 5).
+ * Replaces hyperdepth.pyx `eval_forest` -> hyperdepth.h:253-287 `eval` (rf/forest.h inferencemt + the leaf
+ * reduction HyperdepthLeafFunction::Reduce / argmax / prob_vec, hyperdepth.h:82-131), bit for bit.
+ *
+ * Per pixel (n, row, col) of ims [N][H][W] (u8), row in [row_from, row_to), with the forest of `row`:
+ *   split test: v(h, w) = (float)ims[n][clamp(row + h - 16, 0, H-1)][clamp(col + w - 16, 0, W-1)]; the walk goes to
+ *     `left` iff v(h0, w0) - v(h1, w1) < threshold (f32; a NaN threshold always goes right);
+ *   S[c] = sum over the trees of the reached leaves' counts[c], c < C = n_classes;
+ *   pos  = first index of the maximum of S;  pos2 = first index of the maximum of S without pos
+ *     (with < 2 non-zero classes: none -> pos = 0, pos2 = 1; one -> pos2 = pos == 0 ? 1 : 0);
+ *   out[n][row][col][0] = (float)col - (float)pos / (float)n_disp_bins
+ *   out[n][row][col][1] = (float)S[pos] / (float)sum(S)          (NaN when every count is 0)
+ *   out[n][row][col][2] = |out[..][0] - ((float)col - (float)pos2 / (float)n_disp_bins)|
+ * IEEE f32 division, no contraction.  Rows outside [row_from, row_to) are written NaN.
+ *
+ * Device tables (every pointer in device memory; the struct itself is host memory, read during the call only):
+ *   nodes    [n_nodes][8] int32   split nodes: { threshold (f32 bits), h0, w0, h1, w1, left, right, 0 }
+ *                                 (the file's c0 / c1 are not stored: the reference's samples have one channel)
+ *   roots    [n_rows][n_trees]    root of tree t of image row row0 + r
+ *            a child / root value v >= 0 is node v, v < 0 is leaf ~v (= -v - 1)
+ *   leaf_off [n_leaves + 1] int64 CSR offsets of the leaves' lists into entries (non-decreasing, leaf_off[0] = 0)
+ *   leaf_sum [n_leaves] int32     sum of the leaf's counts
+ *   entries  [n_entries][2] int32 (class, count), classes strictly increasing within a leaf, 0 <= class < n_classes,
+ *                                 count >= 0; zero counts may be left out (the loader stores non-zero ones only)
+ *   max_depth                     the longest root-to-leaf path, in split nodes
+ * The caller guarantees counts >= 0 and that the per-pixel sum of leaf_sum over the trees fits an int32
+ * (connecting_the_dots_amd/hyperdepth.py checks both at load).  Table contents are not validated here, but
+ * malformed tables cannot make the kernel access memory out of bounds or loop forever: a walk longer than max_depth,
+ * a node / leaf index out of range or a leaf list outside entries makes that pixel NaN, and classes outside
+ * [0, n_classes) are skipped.
+ *
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for a NULL pointer (nodes / entries may be NULL when their counts
+ * are 0), N < 0, H or W < 1 or >= 2^24, rows outside 0 <= row_from <= row_to <= H, a non-empty row range outside
+ * [row0, row0 + n_rows), n_trees outside [1, 16], n_classes < 2, n_disp_bins < 1, negative table sizes or max_depth;
+ * CTD_ERR_UNSUPPORTED when 4 * n_classes + 1024 * n_trees > 65536 (the per-workgroup LDS histogram) or the grid
+ * exceeds the launch limits.  No workspace.
+ * -------------------------------------------------------------------------------------- */
+typedef struct ctd_hd_tables {
+  const int32_t* nodes;
+  const int32_t* roots;
+  const int64_t* leaf_off;
+  const int32_t* leaf_sum;
+  const int32_t* entries;
+  int64_t n_nodes, n_leaves, n_entries;
+  int32_t row0, n_rows, n_trees, n_classes, max_depth, reserved;
+} ctd_hd_tables;                 /* 88 bytes */
+int ctd_hyperdepth_eval_f32(const ctd_hd_tables* tables, const uint8_t* ims, int N, int H, int W, int row_from,
+                            int row_to, int n_disp_bins, float* out, int device, void* stream);
 
 #ifdef __cplusplus
 }
