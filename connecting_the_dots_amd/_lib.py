@@ -83,6 +83,13 @@ SIGNATURES = {
     "ctd_render_mesh_proj_f32": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp,
                                           _c_float, _c_float, _vp, _vp, _vp, _c_int, _vp]),
     "ctd_render_mesh_f32": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "ctd_mesh_bvh_bytes": (_c_size_t, [_c_int]),
+    "ctd_mesh_bvh_workspace_bytes": (_c_size_t, [_c_int]),
+    "ctd_mesh_bvh_build_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_size_t, _vp, _c_size_t, _vp, _c_int, _vp]),
+    "ctd_render_mesh_proj_bvh_f32": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int,
+                                              _vp, _vp, _c_float, _c_float, _vp, _vp, _vp, _c_int, _vp]),
+    "ctd_render_mesh_bvh_f32": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp,
+                                         _c_int, _vp]),
     "ctd_syn_finish_f32": (_c_int, [_vp] * 4 + [ctypes.c_double, _c_float, _c_int, _c_float, _c_int] + [_vp] * 5 +
                            [_c_int] * 3 + [_c_int, _vp]),
     "ctd_augment_f32": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp] + [_c_int] * 3 + [_c_int, _vp]),

@@ -646,6 +646,56 @@ int ctd_render_mesh_f32(const float* verts, const float* colors, const float* no
                          (hipStream_t)stream);
 }
 
+size_t ctd_mesh_bvh_bytes(int n_faces) {
+  return n_faces < 0 || n_faces > kBvhMaxFaces ? 0 : mesh_bvh_bytes(n_faces);
+}
+
+size_t ctd_mesh_bvh_workspace_bytes(int n_faces) {
+  return n_faces < 0 || n_faces > kBvhMaxFaces ? 0 : mesh_bvh_workspace_bytes(n_faces);
+}
+
+int ctd_mesh_bvh_build_f32(const float* verts, int n_verts, const int* faces, int n_faces, void* bvh, size_t bvh_bytes,
+                           void* workspace, size_t workspace_bytes, int* depth, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || !bvh) return CTD_ERR_INVALID_ARG;
+  if (n_faces > 0 && (!verts || !faces || !workspace || n_verts == 0)) return CTD_ERR_INVALID_ARG;
+  if ((uintptr_t)bvh % 16 || (uintptr_t)workspace % 16) return CTD_ERR_INVALID_ARG;
+  if (bvh_bytes < mesh_bvh_bytes(n_faces)) return CTD_ERR_INVALID_ARG;
+  if (workspace_bytes < mesh_bvh_workspace_bytes(n_faces)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return mesh_bvh_build_f32(verts, faces, n_faces, bvh, workspace, depth, (hipStream_t)stream);
+}
+
+int ctd_render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, int n_verts, const int* faces,
+                                 int n_faces, const float* cam, int cam_width, int cam_height, const float* proj,
+                                 int proj_width, int proj_height, const float* shader, const float* pattern,
+                                 float d_alpha, float d_beta, float* depth, float* color, float* normal, int device,
+                                 void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || cam_width <= 0 || cam_height <= 0 || proj_width <= 0 ||
+      proj_height <= 0 || (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!bvh || (uintptr_t)bvh % 16 || !cam || !proj || !shader || !pattern || !color ||
+      (n_faces > 0 && (!verts || !colors || !faces)))
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_proj_bvh_f32(bvh, verts, colors, faces, n_faces, cam, cam_width, cam_height, proj, proj_width,
+                                  proj_height, shader, pattern, d_alpha, d_beta, depth, color, normal, (hipStream_t)stream);
+}
+
+int ctd_render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals, int n_verts,
+                            const int* faces, int n_faces, const float* cam, int cam_width, int cam_height,
+                            const float* shader, float* depth, float* color, float* normal, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || cam_width <= 0 || cam_height <= 0 ||
+      (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!bvh || (uintptr_t)bvh % 16 || !cam || !shader || (n_faces > 0 && (!verts || !faces))) return CTD_ERR_INVALID_ARG;
+  if (n_faces > 0 && ((color && !colors) || ((color || normal) && !normals))) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_bvh_f32(bvh, verts, colors, normals, faces, n_faces, cam, cam_width, cam_height, shader, depth,
+                             color, normal, (hipStream_t)stream);
+}
 
 static bool syn_shape_ok(int N, int H, int W) {
   return N >= 0 && N <= 65535 && H > 0 && W > 0 && (double)H * W * 3 < 2147483648.0;

@@ -176,6 +176,20 @@ int render_mesh_f32(const float* verts, const float* colors, const float* normal
                     const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth, float* color, float* normal,
                     hipStream_t stream);
 
+// render_bvh.hip
+constexpr int kBvhMaxFaces = 1 << 28;
+size_t mesh_bvh_bytes(long n_faces);
+size_t mesh_bvh_workspace_bytes(long n_faces);
+int mesh_bvh_build_f32(const float* verts, const int* faces, int n_faces, void* bvh, void* workspace, int* depth,
+                       hipStream_t stream);
+int render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, const int* faces, int n_faces,
+                             const float* cam_p, int cam_w, int cam_h, const float* proj_p, int proj_w, int proj_h,
+                             const float* shader, const float* pattern, float d_alpha, float d_beta, float* depth,
+                             float* color, float* normal, hipStream_t stream);
+int render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals, const int* faces,
+                        int n_faces, const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth,
+                        float* color, float* normal, hipStream_t stream);
+
 
 // synth.hip
 int syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend, double bf,

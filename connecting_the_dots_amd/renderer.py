@@ -14,10 +14,14 @@ everything on the device.  Both renderers of the reference are provided (`mesh_p
 uses, and the plain `mesh`); there is no CPU engine in this package (engine='cpu' raises: the CPU path lives on as
 the test oracle).
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _lib
+
+CTD_ERR_UNSUPPORTED = 3
 
 
 def _cam_params(fx, fy, px, py, R, t):
@@ -44,6 +48,7 @@ class PyShader:
 class PyRenderInput:
     def __init__(self, verts=None, colors=None, normals=None, faces=None):
         self.verts = self.colors = self.normals = self.faces = None
+        self._bvh = None
         if verts is not None:
             self.set_verts(verts)
         if normals is not None:
@@ -62,6 +67,7 @@ class PyRenderInput:
 
     def set_verts(self, verts):
         self.verts = self._nx3(verts, np.float32, 'verts')
+        self._bvh = None                  # PyRenderer(accel='bvh') cache: built from verts and faces
 
     def set_colors(self, colors):
         self.colors = self._nx3(colors, np.float32, 'colors')
@@ -71,11 +77,61 @@ class PyRenderInput:
 
     def set_faces(self, faces):
         self.faces = self._nx3(faces, np.int32, 'faces')
+        self._bvh = None
 
 
-def render_mesh_proj(verts, colors, faces, cam, proj, shader, pattern, d_alpha=1.0, d_beta=0.0):
+class MeshBVH:
+    """Bounding volume hierarchy of one static mesh, built on the device (ctd_mesh_bvh_build_f32) for the `bvh=`
+    argument of render_mesh_proj / render_mesh.  Renders through it are bit-identical to the brute-force caster.
+
+    verts [n,3] f32, faces [m,3] int32: CUDA tensors or numpy (copied to `device`).  The tree belongs to exactly these
+    tensors (kept referenced here): pass `bvh.verts` / `bvh.faces`, or the same tensors, unchanged, to the renderers.
+    `.depth` is the tree depth, `.nbytes` the buffer size, `.n_faces` the face count.  A tree deeper than the
+    traversal stack is not usable (`.usable` False); the renderers then fall back to the brute-force caster."""
+
+    def __init__(self, verts, faces, device=None):
+        dev = torch.device(device) if device is not None else (
+            verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else
+            torch.device("cuda", torch.cuda.current_device()))
+        up = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(dev, dt).contiguous()
+        self.verts, self.faces = up(verts, torch.float32), up(faces, torch.int32)
+        if self.verts.ndim != 2 or self.verts.shape[1] != 3 or self.faces.ndim != 2 or self.faces.shape[1] != 3:
+            raise RuntimeError("verts and faces must be [n,3] and [m,3]")
+        n_verts, self.n_faces = self.verts.shape[0], self.faces.shape[0]
+        if self.n_faces and bool(((self.faces < 0) | (self.faces >= n_verts)).any()):
+            raise RuntimeError("faces index outside [0, %d)" % n_verts)
+        l = _lib.lib()
+        self.nbytes = int(l.ctd_mesh_bvh_bytes(self.n_faces))
+        if self.nbytes == 0:
+            raise RuntimeError("mesh too large for a BVH (%d faces)" % self.n_faces)
+        self.buffer = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(1, int(l.ctd_mesh_bvh_workspace_bytes(self.n_faces))), dtype=torch.uint8, device=dev)
+        depth = ctypes.c_int(0)
+        st = l.ctd_mesh_bvh_build_f32(self.verts.data_ptr(), n_verts, self.faces.data_ptr(), self.n_faces,
+                                      self.buffer.data_ptr(), self.nbytes, ws.data_ptr(), ws.numel(),
+                                      ctypes.byref(depth), dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        self.depth = depth.value
+        self.usable = st == 0
+        if st not in (0, CTD_ERR_UNSUPPORTED):
+            _lib.check(st, "mesh_bvh_build")
+
+    def matches(self, verts, faces):
+        return verts.data_ptr() == self.verts.data_ptr() and faces.data_ptr() == self.faces.data_ptr() and \
+            tuple(verts.shape) == tuple(self.verts.shape) and tuple(faces.shape) == tuple(self.faces.shape)
+
+
+def _check_bvh(bvh, verts, faces):
+    if not isinstance(bvh, MeshBVH):
+        raise TypeError("bvh must be a MeshBVH")
+    if not bvh.matches(verts, faces):
+        raise RuntimeError("bvh was built from other verts / faces tensors")
+    return bvh.usable
+
+
+def render_mesh_proj(verts, colors, faces, cam, proj, shader, pattern, d_alpha=1.0, d_beta=0.0, bvh=None):
     """verts, colors [n,3] f32, faces [m,3] int32, pattern [ph,pw,3] f32: CUDA tensors; cam, proj: PyCamera; shader:
-    PyShader -> (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors (normal zero where nothing is hit)."""
+    PyShader -> (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors (normal zero where nothing is hit).
+    bvh: a MeshBVH of these verts / faces, or None (brute force); both give the same bits."""
     for t_, name, dt in ((verts, "verts", torch.float32), (colors, "colors", torch.float32), (faces, "faces", torch.int32),
                          (pattern, "pattern", torch.float32)):
         if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.is_contiguous() and t_.dtype == dt):
@@ -86,6 +142,14 @@ def render_mesh_proj(verts, colors, faces, cam, proj, shader, pattern, d_alpha=1
     depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
     color = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
     normal = torch.zeros((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
+    if bvh is not None and _check_bvh(bvh, verts, faces):
+        st = _lib.lib().ctd_render_mesh_proj_bvh_f32(
+            bvh.buffer.data_ptr(), verts.data_ptr(), colors.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
+            cam.params.ctypes.data, cam.width, cam.height, proj.params.ctypes.data, proj.width, proj.height,
+            shader.params.ctypes.data, pattern.data_ptr(), float(d_alpha), float(d_beta), depth.data_ptr(),
+            color.data_ptr(), normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "render_mesh_proj (bvh)")
+        return depth, color, normal
     st = _lib.lib().ctd_render_mesh_proj_f32(
         verts.data_ptr(), colors.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
         cam.params.ctypes.data, cam.width, cam.height, proj.params.ctypes.data, proj.width, proj.height,
@@ -95,9 +159,9 @@ def render_mesh_proj(verts, colors, faces, cam, proj, shader, pattern, d_alpha=1
     return depth, color, normal
 
 
-def render_mesh(verts, colors, normals, faces, cam, shader):
+def render_mesh(verts, colors, normals, faces, cam, shader, bvh=None):
     """RenderMeshFunctor (render.h:150-223): verts, colors, normals [n,3] f32, faces [m,3] int32 CUDA tensors ->
-    (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors."""
+    (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors.  bvh: as for render_mesh_proj."""
     for t_, name, dt in ((verts, "verts", torch.float32), (colors, "colors", torch.float32),
                          (normals, "normals", torch.float32), (faces, "faces", torch.int32)):
         if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.is_contiguous() and t_.dtype == dt):
@@ -108,6 +172,13 @@ def render_mesh(verts, colors, normals, faces, cam, shader):
     depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
     color = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
     normal = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
+    if bvh is not None and _check_bvh(bvh, verts, faces):
+        st = _lib.lib().ctd_render_mesh_bvh_f32(
+            bvh.buffer.data_ptr(), verts.data_ptr(), colors.data_ptr(), normals.data_ptr(), verts.shape[0],
+            faces.data_ptr(), faces.shape[0], cam.params.ctypes.data, cam.width, cam.height, shader.params.ctypes.data,
+            depth.data_ptr(), color.data_ptr(), normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "render_mesh (bvh)")
+        return depth, color, normal
     st = _lib.lib().ctd_render_mesh_f32(
         verts.data_ptr(), colors.data_ptr(), normals.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
         cam.params.ctypes.data, cam.width, cam.height, shader.params.ctypes.data, depth.data_ptr(), color.data_ptr(),
@@ -117,11 +188,15 @@ def render_mesh(verts, colors, normals, faces, cam, shader):
 
 
 class PyRenderer:
-    def __init__(self, cam, shader, engine='gpu', n_threads=1, device=None):
+    def __init__(self, cam, shader, engine='gpu', n_threads=1, device=None, accel=None):
+        """accel=None: brute-force ray casting; accel='bvh': a MeshBVH per PyRenderInput, built at its first render and
+        kept until its verts or faces are set again (same output bits either way)."""
         if engine != 'gpu':
             raise Exception('invalid engine' if engine != 'cpu' else
                             "engine='cpu' is not part of this package (the CPU renderer is the test oracle)")
-        self.cam, self.shader = cam, shader
+        if accel not in (None, 'bvh'):
+            raise Exception("invalid accel (None or 'bvh')")
+        self.cam, self.shader, self.accel = cam, shader, accel
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.depth_buffer = np.zeros((cam.height, cam.width), np.float32)
         self.color_buffer = np.zeros((cam.height, cam.width, 3), np.float32)
@@ -141,16 +216,27 @@ class PyRenderer:
         self.color_buffer[...] = c.cpu().numpy()
         self.normal_buffer[...] = n.cpu().numpy()
 
+    def _mesh_tensors(self, input):
+        """(verts, faces, bvh) on the device; with accel='bvh' the tree and its tensors are cached on the input"""
+        up = lambda a: torch.from_numpy(a).to(self.device)
+        if self.accel != 'bvh':
+            return up(input.verts), up(input.faces), None
+        b = input._bvh
+        if b is None or b.verts.device != self.device:
+            b = input._bvh = MeshBVH(input.verts, input.faces, device=self.device)
+        return b.verts, b.faces, b
+
     def mesh(self, input):
         up = lambda a: torch.from_numpy(a).to(self.device)
-        self._store(*render_mesh(up(input.verts), up(input.colors), up(input.normals), up(input.faces), self.cam,
-                                 self.shader))
+        verts, faces, bvh = self._mesh_tensors(input)
+        self._store(*render_mesh(verts, up(input.colors), up(input.normals), faces, self.cam, self.shader, bvh=bvh))
 
     def mesh_proj(self, input, proj, pattern, d_alpha=1, d_beta=0):
         pattern = np.ascontiguousarray(pattern, np.float32)
         if pattern.shape != (proj.height, proj.width, 3):
             raise Exception('pattern has to be a %dx%dx3 tensor' % (proj.height, proj.width))
         up = lambda a: torch.from_numpy(a).to(self.device)
-        d, c, n = render_mesh_proj(up(input.verts), up(input.colors), up(input.faces), self.cam, proj, self.shader,
-                                   up(pattern), d_alpha, d_beta)
+        verts, faces, bvh = self._mesh_tensors(input)
+        d, c, n = render_mesh_proj(verts, up(input.colors), faces, self.cam, proj, self.shader, up(pattern), d_alpha,
+                                   d_beta, bvh=bvh)
         self._store(d, c, n)

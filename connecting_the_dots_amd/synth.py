@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .renderer import PyCamera, PyShader, render_mesh_proj
+from .renderer import MeshBVH, PyCamera, PyShader, render_mesh_proj
 
 # ctd_augment_params of include/ctd_hip.h (32 bytes per image)
 AUGMENT_PARAMS = np.dtype([("blur", "<i4"), ("taps", "<f4", (5,)), ("noise_scale", "<f8")])
@@ -269,7 +269,7 @@ def sample_track_poses(rng, track_length=4, baseline=0.075, blend_im=0.6):
 
 
 def render_track_sample(mesh, patterns, K, rng, track_length=4, blend_im=0.6, baseline=0.075, data_aug=True,
-                        generator=None, sample_id=0, aug_params=None):
+                        generator=None, sample_id=0, aug_params=None, bvh=None):
     """One track of one static scene, on the device: create_syn_data.create_data's per-frame, per-scale loop
     (render_mesh_proj with the reference's shader and decay, then finish_render) followed by TrackSynDataset's
     augmentation (data_aug: every scale's `im`, the draws of dataset.py's settings; with max_shift = 0 disp and grad
@@ -279,11 +279,22 @@ def render_track_sample(mesh, patterns, K, rng, track_length=4, blend_im=0.6, ba
     [H_s,W_s,3] f32 CUDA tensor per scale (scale_patterns); K [3,3] intrinsics of scale 0.  `rng` (numpy RandomState)
     draws the poses and -- unless `generator` is given -- the augmentation.
     Returns the keys of data/dataset.py:57-137 as CUDA tensors: im{s}, ambient{s}, grad{s} [tl,1,H_s,W_s], disp0
-    [tl,1,H,W], R [tl,3,3], t [tl,3], blend_im (f32 scalar), id."""
+    [tl,1,H,W], R [tl,3,3], t [tl,3], blend_im (f32 scalar), id.
+    bvh: None (brute-force ray casting), a renderer.MeshBVH of this mesh, or 'auto' (one tree built here and used for
+    all track_length x scales renders); the result is the same, bit for bit."""
     dev = patterns[0].device
     up = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(dev, dt).contiguous()
     verts, colors, faces = up(mesh["verts"], torch.float32), up(mesh["colors"], torch.float32), up(mesh["faces"],
                                                                                                     torch.int32)
+    if isinstance(bvh, str):
+        if bvh != 'auto':
+            raise ValueError("bvh must be None, 'auto' or a MeshBVH")
+        bvh = MeshBVH(verts, faces, device=dev)
+    elif bvh is not None and not (bvh.verts.shape == verts.shape and bvh.faces.shape == faces.shape and
+                                  torch.equal(bvh.verts, verts) and torch.equal(bvh.faces, faces)):
+        raise RuntimeError("bvh was built from another mesh")
+    if bvh is not None:
+        verts, faces = bvh.verts, bvh.faces
     K = np.asarray(K.cpu() if isinstance(K, torch.Tensor) else K, np.float32)
     poses = sample_track_poses(rng, track_length, baseline, blend_im)
     shader = PyShader(0.5, 1.5, 0.0, 10)                               # create_syn_data.py:155
@@ -298,7 +309,7 @@ def render_track_sample(mesh, patterns, K, rng, track_length=4, blend_im=0.6, ba
             cam = PyCamera(fx, fy, px, py, poses["R"][ind], poses["t"][ind], w, h)
             proj = PyCamera(fx, fy, px, py, poses["R_proj"][ind], poses["t_proj"][ind], w, h)
             frames[s].append(render_mesh_proj(verts, colors, faces, cam, proj, shader, patterns[s], d_alpha=0.0,
-                                              d_beta=0.35))
+                                              d_beta=0.35, bvh=bvh))
     out = {}
     for s in range(n_s):
         depth, color, normal = (torch.stack([f[k] for f in frames[s]]) for k in range(3))

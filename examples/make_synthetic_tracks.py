@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--bvh", action="store_true", 
+                    help="ray-cast through a per-sample BVH (same output, faster on large meshes)")
     args = ap.parse_args()
 
     import numpy as np
@@ -55,8 +57,9 @@ def main():
     rng = np.random.RandomState(args.seed)
     g = torch.Generator(device=dev)
     g.manual_seed(args.seed)
-    synth.render_track_sample(sc, pats, K, rng, track_length=TL, generator=g)          # warm-up (code objects)
-    samples, ms = clock(lambda: [synth.render_track_sample(sc, pats, K, rng, track_length=TL, generator=g, sample_id=b)
+    bvh = "auto" if args.bvh else None
+    synth.render_track_sample(sc, pats, K, rng, track_length=TL, generator=g, bvh=bvh)          # warm-up (code objects)
+    samples, ms = clock(lambda: [synth.render_track_sample(sc, pats, K, rng, track_length=TL, generator=g, sample_id=b, bvh=bvh)
                                  for b in range(args.batch)])
     print("render + finish + augment: %d tracks x %d frames x 4 scales at %dx%d: %.1f ms" % (args.batch, TL, H, W, ms))
     batch, ms = clock(lambda: synth.collate_tracks(samples))

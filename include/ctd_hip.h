@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables, ctd_mesh_bvh_bytes / ctd_mesh_bvh_workspace_bytes / ctd_mesh_bvh_build_f32 / ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -470,6 +470,38 @@ int ctd_render_mesh_f32(const float* verts, const float* colors, const float* no
                         const int* faces, int n_faces, const float* cam, int cam_width, int cam_height,
                         const float* shader, float* depth, float* color, float* normal, int device,
                         void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * BVH ray casting (additive in ABI version 5): the same two renderers over a bounding volume hierarchy built
+ * on the device once per mesh.  Outputs are bit-identical to ctd_render_mesh_proj_f32 / ctd_render_mesh_f32
+ * (same hit face, t, u, v for every ray; the pruning bound is derived in csrc/render_bvh.hip).
+ *   ctd_mesh_bvh_bytes(n) / ctd_mesh_bvh_workspace_bytes(n): sizes of the tree buffer and of the build's
+ *   scratch (0 for n < 0 or n > 2^28).  Both device buffers must be 16-byte aligned.
+ *   ctd_mesh_bvh_build_f32: verts [n_verts][3] f32, faces [n_faces][3] int32 (device; indices are NOT checked,
+ *   they must lie in [0, n_verts)) -> bvh.  Deterministic: the buffer is a pure function of verts/faces, byte for
+ *   byte.  Synchronises `stream` once to read the tree depth into *depth (may be NULL).  Returns
+ *   CTD_ERR_UNSUPPORTED for a tree deeper than the traversal stack (62 levels; the buffer is then complete but
+ *   refused by the renderers -- use the brute-force entries), CTD_ERR_WORKSPACE for a short workspace.
+ *   n_faces == 0 is valid (an empty tree: every pixel is "nothing hit").
+ *   ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32: the arguments of the brute-force entries plus the
+ *   tree.  The tree must have been built from the same verts / faces pointers with the same contents; a stale
+ *   tree gives undefined results.  Each call reads the tree's 64-byte header (a synchronous copy on `stream`)
+ *   and returns CTD_ERR_INVALID_ARG if it is not a tree of n_faces faces, CTD_ERR_UNSUPPORTED if too deep.
+ * -------------------------------------------------------------------------------------- */
+size_t ctd_mesh_bvh_bytes(int n_faces);
+size_t ctd_mesh_bvh_workspace_bytes(int n_faces);
+int ctd_mesh_bvh_build_f32(const float* verts, int n_verts, const int* faces, int n_faces, void* bvh,
+                           size_t bvh_bytes, void* workspace, size_t workspace_bytes, int* depth, int device,
+                           void* stream);
+int ctd_render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, int n_verts,
+                                 const int* faces, int n_faces, const float* cam, int cam_width,
+                                 int cam_height, const float* proj, int proj_width, int proj_height,
+                                 const float* shader, const float* pattern, float d_alpha, float d_beta,
+                                 float* depth, float* color, float* normal, int device, void* stream);
+int ctd_render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals,
+                            int n_verts, const int* faces, int n_faces, const float* cam, int cam_width,
+                            int cam_height, const float* shader, float* depth, float* color, float* normal,
+                            int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Training-sample finishing of the synthetic data path (additive in ABI version 5).
