@@ -4,8 +4,8 @@
 //     NCC = (S_ab - n*ma*mb) / (sa*sb + 1e-8),   S_ab = sum over the bs x bs window of a*b
 // so that each output costs ~20 VALU slots instead of >= 243 and the kernel is bound by
 // the 4 B/output volume store (HBM roofline).  Results agree with the reference order
-// to |a-b| <= 1e-5*|b| + 1e-6 (tests), not bit for bit; bit-exact indices come from the
-// re-rank in ctd_xcorrvol_argmax_f32.
+// to |a-b| <= 1e-5*|b| + 1e-6 (C > 1: the sum of that bound over the channels' NCCs, see the error model above
+// ncc_fixup_kernel), not bit for bit; bit-exact indices come from the re-rank in ctd_xcorrvol_argmax_f32.
 //
 // Work decomposition (one wavefront = 64 product columns, 4 disparities per lane):
 //   * a workgroup is 4 consumer wavefronts (16 adjacent disparities of one column tile)
@@ -96,7 +96,7 @@ struct PrepassJob {
 // BSC > 0: compile-time block size (tap loops unrolled); BSC == 0: run-time `bs_rt`
 // F32 (round 4, block 9): the window sums in f32 on samples CENTRED by the image's constant (the planes hold centred
 // values anyway): sum of squared deviations = s2' - s1' * mean', whose relative error is ~F * 2^-24 * (number of
-// roundings) with F = s2' / var = 1 + n (mean - centring)^2 / var -- the very factor the listing rule bounds by sqrt(8)
+// roundings) with F = s2' / var = 1 + n (mean - centring)^2 / var -- the very factor the listing rule bounds by 1 + kFlagRatio
 // (windows above it are recomputed by the fix-up pass), so unlisted windows keep their reciprocal deviation to ~1e-6
 // relative, well inside the fast path's error budget; the raw mean for the flat-window test is mean' + centring.  Half the
 // LDS, no f32 -> f64 conversions, full-rate additions.
@@ -205,14 +205,14 @@ __global__ __launch_bounds__(kSTW* kSRows) void ncc_prepass_kernel(PrepassJob ja
     // Windows whose outputs the fast kernel cannot deliver within tolerance are listed for ncc_fixup_kernel
     // (see there), which recomputes EVERY output they take part in:
     //  * deviation small against the offset from the centring constant: cov = S_ab - n*ma*mb cancels in f32;
-    //  * (nearly) flat window, deviation below 2e-4 of its mean: the reference's own value is then decided by
+    //  * (nearly) flat window, rms deviation below 6.3e-4 of its mean (kFlatRatio): the reference's own value is then decided by
     //    the rounding of its mean (ext.h:157-158) and only the same operation order reproduces it; or deviation
     //    below kDevFloor, where the 1e-8 of the reference's denominator stops being a small correction.
     // A listed window's reciprocal deviation is stored as 0: the fast kernels then produce the placeholder score 0 for
     // exactly the outputs the fix-up pass overwrites (finite, so the in-kernel ranking's integer keys stay ordered;
     // what the ranking does about placeholders: see the all-D kernel).
     const double mc = F32 ? mean_c : mean - (double)cval;
-    const bool flat = 4e-8 * n * mean * mean > var || var < kDevFloor * kDevFloor;
+    const bool flat = kFlatRatio * n * mean * mean > var || var < kDevFloor * kDevFloor;
     const bool listed = flat || n * mc * mc > jp.flag_ratio * var;
     // reciprocal deviation (see ncc_inv_norm): v_rsq_f32 and one Newton step in f32, 1e-7 relative -- the f64 square
     // root and the two f64 divisions this line and `mean` used to cost were 60 % of the kernel's instructions
@@ -242,12 +242,17 @@ __global__ __launch_bounds__(kSTW* kSRows) void ncc_prepass_kernel(PrepassJob ja
 // Fix-up pass of the fast path.
 //
 // Error model of the fast kernel (tools/err_vs_factor.py): cov = S_ab - n*ma*mb is formed from values
-// centred by one constant per image, so |fast - exact| <~ c * 2^-24 * sqrt(Fa * Fb) with
-// F = 1 + n*(window mean - centring)^2 / (sum of squared deviations) per window and c <= ~6 (ten f32
-// roundings along the longest summation path).  The contract |a-b| <= 1e-5|b| + 1e-6 therefore holds
-// whenever Fa * Fb <= 8; LCN'd input has F ~ 1 except in flat regions and in the low-variance windows clamped
-// to column 0.  The pre-pass lists every window with F > sqrt(8) (and marks it with a NaN deviation); this kernel
-// visits the listed windows and recomputes every output they take part in in the reference's operation order
+// centred by one constant per image, so |fast - exact| <~ c * 2^-24 * sqrt(Fa * Fb) per channel with
+// F = 1 + n*(window mean - centring)^2 / (sum of squared deviations) per window and c <= ~7 (ten f32
+// roundings along the longest summation path; 6.3 measured on clipped plateaus, tests/test_matcher_bounds_gpu.py),
+// plus |NCC| * 1e-8 / (sa * sb) for the reference denominator's 1e-8, which kDevFloor keeps <= 2.1e-6 relative.
+// The pre-pass lists every window with F - 1 > kFlagRatio / C (and marks it with a zero reciprocal deviation), so an
+// unlisted output has sum_c sqrt(Fa * Fb) <= C + kFlagRatio, and kFlagRatio = 1.39 makes 7 * 2^-24 * (C + 1.39)
+// <= C * 1e-6: the contract |a-b| <= 1e-5|b| + 1e-6 holds for C = 1, and for C > 1 the sum of the per-channel bounds,
+// 1e-5 * sum_c |b_c| + C * 1e-6 (include/ctd_hip.h) -- where channels cancel, the reference order's own rounding of
+// its C channels (1.6e-6 from float64 at C = 2) already exceeds a single 1e-6.  LCN'd input has F ~ 1 except in flat
+// regions and in the low-variance windows clamped to column 0.  This kernel visits the listed windows and recomputes
+// every output they take part in in the reference's operation order
 // (bit-identical to CTD_NCC_EXACT).
 // One wavefront per listed window, lane <-> disparity; the window itself (FIX, bs x bs) and the rows of
 // the other image it meets over all disparities (SPAN, bs x (bs + D - 1)) are staged in LDS per channel.

@@ -9,7 +9,9 @@ the test oracle only).
 Additive API (no reference counterpart): `xcorrvol_batch`, `argmax_disp`,
 `xcorrvol_argmax`, `lcn`, ... and the keyword `algo` of the ops that have two kernel families:
     'fast'  (default) tolerance-level kernels, |a-b| <= 1e-5*|b| + 1e-6 against the reference (LDS-tiled, HBM- or
-            issue-bound; f32 and odd block sizes up to 9 -- anything else runs the reference-order kernels);
+            issue-bound; f32 and odd block sizes up to 9 -- anything else runs the reference-order kernels); the NCC
+            volume of C > 1 channels is within the sum of that bound over its per-channel NCCs, 1e-5 * sum_c |b_c| +
+            C * 1e-6 (include/ctd_hip.h);
     'exact' the reference's operation order, bit-identical to its CPU build (the parity anchor).
 The default can be changed with the environment variables CTD_NCC_ALGO (xcorrvol family) and CTD_PHOTO_ALGO
 (photometric loss, cost volumes, pattern similarity loss).

@@ -204,3 +204,64 @@ def lcn(x, radius, eps, dtype=torch.float64):
     var = ex2 - avg ** 2 + 1e-6
     std = torch.sqrt(var) + eps
     return Ref(((d - avg) / std, std), {}, {"avg": avg, "ex2": ex2, "var": var})
+
+
+def _xcorr_windows(x, bs, left, right):
+    """x [B,C,H,W] -> centred windows [B,C,n,H,Wout] and their sums of squared deviations [B,C,H,Wout]: replicate rows,
+    columns padded by replicate `left` / `right` (the clamp of an unclamped column), two-pass mean and deviation"""
+    B, C, H, W = x.shape
+    h = bs // 2
+    xp = F.pad(x.reshape(B * C, 1, H, W), (left, right, h, bs - 1 - h), mode="replicate")
+    win = F.unfold(xp, bs).view(B, C, bs * bs, H, -1)
+    win = win - win.mean(2, keepdim=True)
+    return win, (win * win).sum(2)
+
+
+def xcorrvol(in0, in1, n_disps, block_size, dtype=torch.float64, budget=1 << 25):
+    """XCorrVolFunctor (ext.h:120-191) as stock torch ops on in0's device: in0 [C,H,W] or [N,C,H,W], in1 [C,H,W] ->
+    [D,H,W] or [N,D,H,W], out[d,h,w] = sum_c dot / (sqrt(s0 s1) + 1e-8) over the bs x bs windows centred at (h, w) of
+    in0 and (h, w - d) of in1.  Rows clamp; the pattern's columns are shifted by d BEFORE they clamp (ext.h:152), so
+    its windows are taken over the unclamped columns x = -(D-1) .. W-1.  Disparities are processed in chunks of at most
+    `budget` window elements."""
+    squeeze = in0.dim() == 3
+    a = (in0.unsqueeze(0) if squeeze else in0).to(dtype)
+    b = in1.to(device=a.device, dtype=dtype).unsqueeze(0)
+    N, C, H, W = a.shape
+    D, bs = int(n_disps), int(block_size)
+    h = bs // 2
+    wa, sa = _xcorr_windows(a, bs, h, bs - 1 - h)              # [N,C,n,H,W], [N,C,H,W]
+    wb, sb = _xcorr_windows(b, bs, D - 1 + h, bs - 1 - h)               # [1,C,n,H,W+D-1]: column x at index x + D - 1
+    # offset j = D - 1 - d of the W-wide view starting at index j is the pattern at x = w - d
+    vb, vs = wb.unfold(-1, W, 1), sb.unfold(-1, W, 1)         # [1,C,n,H,D,W], [1,C,H,D,W]
+    out = torch.empty((N, D, H, W), dtype=dtype, device=a.device)
+    chunk = max(1, budget // max(1, N * C * bs * bs * H * W))
+    for d0 in range(0, D, chunk):
+        d1 = min(D, d0 + chunk)
+        js = slice(D - d1, D - d0)                             # offsets of d = d1-1 .. d0
+        dot = (wa.unsqueeze(-2) * vb[..., js, :]).sum(2)       # [N,C,H,dc,W]
+        den = torch.sqrt(sa.unsqueeze(-2) * vs[..., js, :]) + 1e-8
+        val = (dot / den).sum(1).flip(-2)                      # [N,H,dc,W], d ascending
+        out[:, d0:d1] = val.permute(0, 2, 1, 3)
+    return out[0] if squeeze else out
+
+
+def costvol(im, pattern, n_disps, block_size, type, eps, dtype=torch.float64, chunk=32):
+    """The SAD / MSE / soft-census cost volume by composition, as oracle.costvol builds it from the reference's loss:
+    cost[f,d] = block_loss(P_d, im[f]) with P_d[h,x] = P[h, clamp(x-d)].  im [H,W] | [N,H,W], pattern [H,W] | [N,H,W]
+    -> [D,H,W] | [N,D,H,W], in `dtype` on im's device."""
+    squeeze = im.dim() == 2
+    a = (im.unsqueeze(0) if squeeze else im).to(dtype)
+    N, H, W = a.shape
+    p = pattern.to(device=a.device, dtype=dtype)
+    p = p.expand(N, H, W) if p.dim() == 2 else p
+    D = int(n_disps)
+    out = torch.empty((N, D, H, W), dtype=dtype, device=a.device)
+    cols = torch.arange(W, device=a.device)
+    for f in range(N):
+        for d0 in range(0, D, chunk):
+            ds = torch.arange(d0, min(D, d0 + chunk), device=a.device)
+            idx = (cols[None, :] - ds[:, None]).clamp(0, W - 1)          # [dc, W]
+            pd = p[f][:, idx].permute(1, 0, 2).unsqueeze(1)            # [dc,1,H,W]
+            ta = a[f].expand(len(ds), 1, H, W)
+            out[f, d0:d0 + len(ds)] = block_loss(pd, ta, block_size, type, eps)[0][:, 0]
+    return out[0] if squeeze else out

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import f64_refs as R
+from tests import matcher_traps as MT
 from tests.util import assert_close, golden
 
 
@@ -161,3 +162,125 @@ def test_lcn_ref_vs_oracle(oracle, radius):
         y, s = R.lcn(t(x), radius, 0.05).value
         assert_close(s.numpy(), s0, what="std r%d" % radius)
         assert_close(y.numpy(), y0, rtol=2e-5, atol=2e-6, what="lcn r%d" % radius)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the matcher references: f64_refs.xcorrvol / costvol, and the listing-rule classifier of tests/matcher_traps.py
+# ---------------------------------------------------------------------------------------------------------------------
+def _ncc_close(got, ref, C, what):
+    """NCC volumes sum C terms of magnitude <= 1: 1e-12 relative, with C * 1e-12 as the floor near zero"""
+    assert_close(got, ref, rtol=1e-12, atol=1e-12 * C, what=what)
+
+
+def test_xcorrvol_ref_vs_oracle_f64_and_goldens():
+    """every case of the committed reference volumes: the f64 ones to 1e-12, the f32 ones to their own rounding; and
+    the oracle's f64 instantiation on the same (f32-valued) inputs to 1e-12"""
+    from oracle import oracle
+    g = golden("xcorrvol_small")
+    for k, (C, H, W, D, bs) in enumerate(g["cases"]):
+        a, b = g["in0_%d" % k], g["in1_%d" % k]
+        vol = R.xcorrvol(t(a), t(b), int(D), int(bs))
+        assert vol.dtype == torch.float64 and vol.shape == (D, H, W)
+        if a.dtype == np.float64:
+            _ncc_close(vol.numpy(), g["vol_%d" % k], C, "golden %d" % k)
+        else:
+            assert_close(vol.numpy(), g["vol_%d" % k], what="golden %d (f32)" % k)
+        o64 = oracle.xcorrvol(a.astype(np.float64), b.astype(np.float64), int(D), int(bs))
+        _ncc_close(vol.numpy(), o64, C, "oracle f64 %d" % k)
+
+
+@pytest.mark.parametrize("name", ["staircase", "flat", "clipped255", "scale+3", "chan_cancel"])
+def test_xcorrvol_ref_vs_oracle_f64_on_traps(name):
+    """batched frames, the left-border run (D > W / 2), odd and even block sizes, on trap frames with DC offsets"""
+    from oracle import oracle
+    from tests import matcher_traps as T
+    C = 2 if name == "chan_cancel" else 1
+    gen = {**T.NCC_GENERATORS, **T.MULTICHANNEL_GENERATORS}[name]
+    for bs, D in ((9, 23), (4, 7)):
+        frames, pat = gen(5, 2, C, 13, 37, bs)
+        vol = R.xcorrvol(t(frames), t(pat), D, bs, budget=1 << 16).numpy()
+        for f in range(2):
+            o64 = oracle.xcorrvol(frames[f].astype(np.float64), pat.astype(np.float64), D, bs)
+            _ncc_close(vol[f], o64, C, "%s bs %d frame %d" % (name, bs, f))
+
+
+def test_costvol_ref_vs_golden():
+    """the composition of block_loss against the reference's own (f32) composition: within its f32 rounding"""
+    g = golden("costvol")
+    for ty, name in enumerate(R.PHOTO_TYPES):
+        vol = R.costvol(t(g["im"]), t(g["pat"]), int(g["D"]), int(g["bs"]), name, float(np.float32(0.5)))
+        assert vol.dtype == torch.float64
+        assert_close(vol.numpy(), g["vol_%d" % ty], rtol=2e-6, atol=1e-7, what=name)
+        assert np.array_equal(vol.numpy().argmin(0), g["argmin_%d" % ty]), name
+
+
+def test_costvol_ref_per_frame_pattern():
+    """[N,H,W] frames against a shared and a per-frame pattern: each frame's slice is the single-frame volume"""
+    rs = np.random.RandomState(4)
+    im, pat = t(rs.rand(2, 9, 30).astype(np.float32)), t(rs.rand(2, 9, 30).astype(np.float32))
+    shared = R.costvol(im, pat[0], 12, 5, "census_sad", 0.5, chunk=5)
+    per = R.costvol(im, pat, 12, 5, "census_sad", 0.5, chunk=5)
+    for f in range(2):
+        assert torch.equal(shared[f], R.costvol(im[f], pat[0], 12, 5, "census_sad", 0.5))
+        assert torch.equal(per[f], R.costvol(im[f], pat[f], 12, 5, "census_sad", 0.5))
+
+
+def _recount(img, bs, cols, C):
+    """the listing rule window by window, straight from the reference's clamp formulas (ext.h:145-160)"""
+    from tests import matcher_traps as T
+    H, W = img.shape
+    n, h = bs * bs, bs // 2
+    x = img.astype(np.float64)
+    cval = float(np.float32(sum(x[min(max(H // 2 + k // bs - h, 0), H - 1), min(max(W // 2 + k % bs - h, 0), W - 1)]
+                                for k in range(n)) / n))
+    out = np.empty((H, len(cols)), np.int8)
+    for r in range(H):
+        for i, c in enumerate(cols):
+            v = np.array([x[min(max(r + bh - h, 0), H - 1), min(max(c + bw - h, 0), W - 1)]
+                          for bh in range(bs) for bw in range(bs)])
+            m = v.mean()
+            V = ((v - m) ** 2).sum()
+            st = {"f1": np.array(n * (m - cval) ** 2 / V if V > 0 else np.inf), "dev": np.array(np.sqrt(V)),
+                  "flat": np.array(T.K_FLAT * n * m * m / V if V > 0 else np.inf)}
+            out[r, i] = T.window_class(st, T.K_FLAG_RATIO / C)
+    return out
+
+
+@pytest.mark.parametrize("name", ["staircase", "devfloor", "flat", "dots"])
+def test_classifier_vs_recount(name):
+    """classify() against a direct per-window recount, frame side and pattern side (unclamped columns, the left-border
+    run included), on a frame that has windows in all three classes"""
+    from tests import matcher_traps as T
+    bs, D = 5, 9
+    frames, pat = T.NCC_GENERATORS[name](1, 1, 1, 11, 45, bs)
+    cls, sqrtF, floor = T.classify(frames, pat, D, bs)
+    ca = _recount(frames[0, 0], bs, range(45), 1)
+    cb = _recount(pat[0], bs, range(-(D - 1), 45), 1)
+    want = np.stack([np.maximum(ca, cb[:, np.arange(45) - d + D - 1]) for d in range(D)])
+    assert np.array_equal(cls[0], want), name
+    assert (sqrtF >= 1).all() and (floor > 0).all()
+    if name == "staircase":
+        assert {T.LISTED, T.GUARDED, T.UNLISTED} <= set(np.unique(cls).tolist())
+
+
+@pytest.mark.parametrize("bs,H,W", [shape[:3] for shape in MT.NCC_SHAPES])
+def test_trap_placement(bs, H, W):
+    """at the GPU suite's own seeds and shapes, the generators put interior windows where they say: F - 1 at
+    kFlagRatio / C * r (staircase, C = 1, 2, 3), deviation at kDevFloor * r (devfloor), kFlatRatio n mean^2 / V at r
+    (every flat level), for r in 0.9, 0.98, 1.02, 1.1 -- and the staircase's centring window lies inside its level-0
+    band, so cval is the tile's mean"""
+    from tests import matcher_traps as T
+    cases = [("staircase", C, "f1", lambda r, C=C: T.K_FLAG_RATIO / C * r) for C in (1, 2, 3)]
+    cases += [("devfloor", 1, "dev", lambda r: T.K_DEV_FLOOR * r)]
+    cases += [(name, 1, "flat", lambda r: r) for name in T.FLAT_LEVELS]
+    gens = {**T.NCC_GENERATORS, **T.MULTICHANNEL_GENERATORS}
+    for name, C, key, target in cases:
+        frames, pat = gens[name](T.trap_seed(bs, H, C), 2, C, H, W, bs)
+        for img in (frames[0], frames[1], pat):
+            st = T.window_stats(img, bs)
+            if name == "staircase":
+                assert np.abs(st["cval"]).max() < 1e-6, (name, C, bs)
+            h = bs // 2                                        # windows clear of the border clamps
+            vals = st[key][:, h:H - h, h:W - h].ravel()
+            for r in T.RATIOS:
+                assert np.isclose(vals, target(r), rtol=2e-3).any(), (name, C, bs, r)
