@@ -27,6 +27,19 @@ class HdTables(ctypes.Structure):
                 ("row0", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_trees", ctypes.c_int32),
                 ("n_classes", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
+class HdTrainParams(ctypes.Structure):
+    """ctd_hd_train_params of include/ctd_hip.h"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_trees", "max_tree_depth", "n_test_split_functions",
+                                              "n_test_thresholds", "n_test_samples", "min_samples_to_split",
+                                              "min_samples_for_leaf", "depth_switch", "n_disp_bins", "reserved")] + \
+        [("seed", ctypes.c_uint64)]
+
+
+class HdTrainOut(ctypes.Structure):
+    """ctd_hd_train_out of include/ctd_hip.h (device output buffers of a training call and their capacities)"""
+    _fields_ = [("nodes", _vp), ("roots", _vp), ("leaf_off", _vp), ("leaf_sum", _vp), ("entries", _vp), ("used", _vp),
+                ("cap_nodes", ctypes.c_int64), ("cap_leaves", ctypes.c_int64), ("cap_entries", ctypes.c_int64)]
+
 # name -> (restype, argtypes); mirrors include/ctd_hip.h one to one
 SIGNATURES = {
     "ctd_version": (_c_int, []),
@@ -100,6 +113,10 @@ SIGNATURES = {
     "ctd_proj_nn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_vp, _c_int, _vp]),
     "ctd_proj_nn_f64": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_vp, _c_int, _vp]),
     "ctd_hyperdepth_eval_f32": (_c_int, [ctypes.POINTER(HdTables), _vp] + [_c_int] * 6 + [_vp, _c_int, _vp]),
+    "ctd_hyperdepth_train_count_f32": (_c_int, [_vp] + [_c_int] * 6 + [_vp, _c_int, _vp]),
+    "ctd_hyperdepth_train_workspace_bytes": (_c_size_t, [ctypes.POINTER(HdTrainParams), _c_int, _vp, ctypes.c_int64]),
+    "ctd_hyperdepth_train_f32": (_c_int, [ctypes.POINTER(HdTrainParams), _vp, _c_int, _vp, _vp] + [_c_int] * 5 +
+                                 [_vp, _vp, _c_size_t, ctypes.POINTER(HdTrainOut), _c_int, _vp]),
 }
 
 # measurement hooks of include/ctd_hip_bench.h (bench.py, tools/): not part of the drop-in interface

@@ -206,4 +206,13 @@ long hyperdepth_grid(int N, int H, int W);
 int hyperdepth_eval_f32(const ctd_hd_tables& tab, const uint8_t* ims, int N, int H, int W, int row_from, int row_to,
                         int n_disp_bins, float* out, hipStream_t stream);
 
+// hyperdepth_train.hip
+size_t hyperdepth_train_workspace_bytes(const ctd_hd_train_params& p, int R, const int64_t* counts,
+                                        long long cap_leaves);
+int hyperdepth_train_count_f32(const float* disps, int N, int H, int W, int row_from, int row_to, int nb,
+                               int64_t* counts, hipStream_t stream);
+int hyperdepth_train_f32(const ctd_hd_train_params& p, const int64_t* X, const uint8_t* ims, const float* disps, int N,
+                         int H, int W, int row_from, int row_to, const int64_t* counts, void* ws, size_t ws_bytes,
+                         const ctd_hd_train_out& out, hipStream_t stream);
+
 }  // namespace ctd

@@ -1,4 +1,4 @@
-"""HyperDepth random-forest disparity evaluation on the device.
+"""HyperDepth random-forest disparity evaluation and training on the device.
 
 The reference's `hyperdepth/` module (the random-forest baseline the paper compares against) trains one forest per
 image row and evaluates it on the CPU: hyperdepth.h:253-287 `eval`, through rf/forest.h `inferencemt`.  Here:
@@ -7,6 +7,9 @@ image row and evaluates it on the CPU: hyperdepth.h:253-287 `eval`, through rf/f
     HyperDepthForests.from_prefix(prefix, rows, device)   packs the forests of a row range into device tables, once
     forests.eval(ims, n_disp_bins, row_from, row_to)      -> [N, H, W, 3] f32 (disp, prob, |disp - disp2|), one launch
     eval_forest(ims, disps, ...)                          drop-in for hyperdepth.pyx `eval_forest` (numpy in and out)
+    HyperDepthForests.train(ims, disps, TrainParams(), ...)  trains the forests of a row range on the device
+    forests.to_forests()                                  -> the host Forest list (file pre-order), for save_forest
+    train_forest(params, ims, disps, ...)                 drop-in for hyperdepth.pyx `train_forest` (numpy in, files out)
 
 The kernel is ctd_hyperdepth_eval_f32 (include/ctd_hip.h states the semantics and the table layout); its output is
 bit-identical to the reference's.  Differences from the reference, all on inputs it leaves undefined or that this
@@ -15,7 +18,11 @@ port does not support:
   - the loader raises on: an unknown node type, a forest without trees, leaves of one forest with different class
     counts, fewer than 2 classes, negative counts, split offsets beyond 2^20, per-pixel count sums that could overflow
     an int32, a truncated file or trailing bytes; `from_prefix` raises when the rows' class counts disagree;
-  - training (`train_forest`) is not provided.
+  - training draws its randomness from a counter-based generator keyed by a seed (the reference seeds std::mt19937
+    from std::random_device), and scores a split with an exact int64 entropy cost; include/ctd_hip.h
+    (ctd_hyperdepth_train_f32) states the whole contract, tests/hyperdepth_train_ref.py restates it in numpy.
+    Trained forests therefore differ from the reference's run by run, as its own runs differ from each other;
+    tests/test_hyperdepth_train_gpu.py compares their held-out quality with recorded reference runs.
 There is no CPU path: a missing library or GPU is an error.
 """
 import ctypes
@@ -30,6 +37,8 @@ from . import _lib
 PATCH_HALF = 16            # RawSample::at: the reference's 32 x 32 patch is centred on the pixel (hyperdepth.h:190)
 MAX_OFFSET = 1 << 20       # |h|, |w| beyond this are rejected (the reference's int arithmetic could overflow)
 MAX_TREES = 16             # kernel limit (ctd_hyperdepth_eval_f32)
+MAX_TRAIN_DEPTH = 24       # ctd_hyperdepth_train_f32 limits
+MAX_TEST_SAMPLES = 8192
 INT32_MAX = (1 << 31) - 1
 _I4 = np.dtype("<i4")
 
@@ -352,3 +361,184 @@ def eval_forest(ims, disps, n_disp_bins=10, depth_switch=0, n_threads=18, forest
     forests = HyperDepthForests.from_prefix(forest_prefix, range(r0, r1), dev)
     out = forests.eval(torch.from_numpy(ims).to(dev), n_disp_bins, r0, r1)
     return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# training (ctd_hyperdepth_train_f32 of include/ctd_hip.h)
+# ------------------------------------------------------------------------------------------------------------------
+@dataclass
+class TrainParams:
+    """hyperdepth.pyx `TrainParams`: the same names and defaults.  print_node_info is accepted and ignored."""
+    n_trees: int = 6
+    max_tree_depth: int = 8
+    n_test_split_functions: int = 50
+    n_test_thresholds: int = 10
+    n_test_samples: int = 4096
+    min_samples_to_split: int = 16
+    min_samples_for_leaf: int = 8
+    print_node_info: int = 100
+
+    def __str__(self):
+        return ("n_trees=%d, max_tree_depth=%d, n_test_split_functions=%d, n_test_thresholds=%d, n_test_samples=%d, "
+                "min_samples_to_split=%d, min_samples_for_leaf=%d" %
+                (self.n_trees, self.max_tree_depth, self.n_test_split_functions, self.n_test_thresholds,
+                 self.n_test_samples, self.min_samples_to_split, self.min_samples_for_leaf))
+
+
+def x_log_x_table(n):
+    """The contract's cost table X[0..n]: int64(rint(x * log(x) * 2^32)), X[0] = X[1] = 0, in float64 on the host."""
+    x = np.arange(n + 1, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = x * np.log(x) * 2.0 ** 32
+    v[:2] = 0
+    return np.rint(v).astype(np.int64)
+
+
+def check_train_args(params, N, H, W, n_disp_bins, row_from, row_to):
+    """The restrictions of ctd_hyperdepth_train_f32, as ValueError; returns the row range."""
+    p = params
+    lim = [("n_trees", p.n_trees, 1, MAX_TREES), ("max_tree_depth", p.max_tree_depth, 0, MAX_TRAIN_DEPTH),
+           ("n_test_split_functions", p.n_test_split_functions, 0, (1 << 20) - 1),
+           ("n_test_thresholds", p.n_test_thresholds, 0, (1 << 16) - 1),
+           ("n_test_samples", p.n_test_samples, 1, MAX_TEST_SAMPLES),
+           ("min_samples_to_split", p.min_samples_to_split, 0, INT32_MAX),
+           ("min_samples_for_leaf", p.min_samples_for_leaf, 1, INT32_MAX)]
+    for name, v, lo, hi in lim:
+        if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+            raise ValueError("%s = %r: must be an integer in [%d, %d]" % (name, v, lo, hi))
+    if not (isinstance(n_disp_bins, (int, np.integer)) and n_disp_bins >= 1):
+        raise ValueError("n_disp_bins must be >= 1")
+    if W * n_disp_bins > INT32_MAX:
+        raise ValueError("W * n_disp_bins must be below 2^31")
+    if min(N, H, W) < 1 or H >= 1 << 24 or W >= 1 << 24 or N * H * W > INT32_MAX:
+        raise ValueError("ims [N, H, W] must be non-empty, H, W < 2^24 and N * H * W < 2^31")
+    r0 = 0 if row_from < 0 else row_from
+    r1 = H if (row_to > H or row_to < 0) else row_to
+    if r0 >= r1:
+        raise ValueError("empty row range [%d, %d)" % (r0, r1))
+    return r0, r1
+
+
+def _train(cls, ims, disps, params, n_disp_bins=10, depth_switch=0, row_from=-1, row_to=-1, seed=0, device=None):
+    """HyperDepthForests.train: see there."""
+    if not (isinstance(ims, torch.Tensor) and ims.dtype == torch.uint8 and ims.dim() == 3):
+        raise ValueError("ims must be a uint8 tensor [N, H, W]")
+    if not (isinstance(disps, torch.Tensor) and disps.dtype == torch.float32 and disps.shape == ims.shape):
+        raise ValueError("disps must be a float32 tensor of the shape of ims")
+    dev = ims.device if device is None else torch.device(device)
+    if dev.type != "cuda" or ims.device != dev or disps.device != dev:
+        raise RuntimeError("ims and disps must live on one GPU device")
+    N, H, W = ims.shape
+    r0, r1 = check_train_args(params, N, H, W, n_disp_bins, row_from, row_to)
+    R, T, D = r1 - r0, params.n_trees, params.max_tree_depth
+    ims, disps = ims.contiguous(), disps.contiguous()
+    L = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    counts_d = torch.empty(R, dtype=torch.int64, device=dev)
+    _lib.check(L.ctd_hyperdepth_train_count_f32(disps.data_ptr(), N, H, W, r0, r1, int(n_disp_bins),
+                                                 counts_d.data_ptr(), dev.index, stream), "hyperdepth train count")
+    counts = counts_d.cpu().numpy()
+    splits = sum(T * min((1 << D) - 1, max(int(n) - 1, 0)) for n in counts)
+    cap_nodes, cap_leaves, cap_entries = splits, splits + R * T, T * int(counts.sum())
+    p = _lib.HdTrainParams(T, D, params.n_test_split_functions, params.n_test_thresholds, params.n_test_samples,
+                           params.min_samples_to_split, params.min_samples_for_leaf, int(depth_switch),
+                           int(n_disp_bins), 0, int(seed) & ((1 << 64) - 1))
+    counts_h = np.ascontiguousarray(counts, np.int64)
+    ws_bytes = L.ctd_hyperdepth_train_workspace_bytes(ctypes.byref(p), R, counts_h.ctypes.data, cap_leaves)
+    if ws_bytes == 0:
+        raise ValueError("hyperdepth train: arguments refused")
+    t = {"nodes": torch.empty((max(cap_nodes, 1), 8), dtype=torch.int32, device=dev),
+         "roots": torch.empty((R, T), dtype=torch.int32, device=dev),
+         "leaf_off": torch.empty(cap_leaves + 1, dtype=torch.int64, device=dev),
+         "leaf_sum": torch.empty(cap_leaves, dtype=torch.int32, device=dev),
+         "entries": torch.empty((max(cap_entries, 1), 2), dtype=torch.int32, device=dev)}
+    used = torch.zeros(5, dtype=torch.int64, device=dev)
+    X = torch.from_numpy(x_log_x_table(params.n_test_samples)).to(dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = _lib.HdTrainOut(t["nodes"].data_ptr(), t["roots"].data_ptr(), t["leaf_off"].data_ptr(),
+                          t["leaf_sum"].data_ptr(), t["entries"].data_ptr(), used.data_ptr(), cap_nodes, cap_leaves,
+                          cap_entries)
+    _lib.check(L.ctd_hyperdepth_train_f32(ctypes.byref(p), X.data_ptr(), X.numel(), ims.data_ptr(), disps.data_ptr(),
+                                          N, H, W, r0, r1, counts_h.ctypes.data, ws.data_ptr(), ws_bytes,
+                                          ctypes.byref(out), dev.index, stream), "hyperdepth train")
+    n_nodes, n_leaves, n_entries, max_depth, err = (int(v) for v in used.cpu())
+    if err:
+        raise RuntimeError("hyperdepth train: output capacity exceeded (a bound of include/ctd_hip.h failed)")
+    t["nodes"], t["leaf_off"] = t["nodes"][:n_nodes], t["leaf_off"][:n_leaves + 1]
+    t["leaf_sum"], t["entries"] = t["leaf_sum"][:n_leaves], t["entries"][:n_entries]
+    return cls._from_tables(t, r0, T, W * int(n_disp_bins), max_depth, dev)
+
+
+def _from_tables(cls, tensors, row0, n_trees, n_classes, max_depth, device):
+    """A HyperDepthForests over device tables already in the ctd_hd_tables layout (a training call's output)."""
+    self = cls.__new__(cls)
+    self.device = device
+    self.row0, self.n_rows, self.n_trees = row0, tensors["roots"].shape[0], n_trees
+    self.n_classes, self.max_depth = n_classes, max_depth
+    self.tensors = tensors
+    ptr = lambda x: x.data_ptr() if x.numel() else None     # noqa: E731
+    self._tables = HdTables(ptr(tensors["nodes"]), tensors["roots"].data_ptr(), tensors["leaf_off"].data_ptr(),
+                            ptr(tensors["leaf_sum"]), ptr(tensors["entries"]), tensors["nodes"].shape[0],
+                            tensors["leaf_sum"].shape[0], tensors["entries"].shape[0], row0, self.n_rows, n_trees,
+                            n_classes, max_depth, 0)
+    return self
+
+
+def _to_forests(self):
+    """The host Forest of every row, trees in the file's pre-order, leaves with the header n_classes_ = -1 and
+    n_counts = the class count: what the reference's trainer writes (save_forest gives its file)."""
+    h = {k: v.cpu().numpy() for k, v in self.tensors.items()}
+    nodes, off, sums, ents = h["nodes"], h["leaf_off"], h["leaf_sum"], h["entries"]
+    forests = []
+    for r in range(self.n_rows):
+        trees = []
+        for t in range(self.n_trees):
+            lst = []
+
+            def emit(v):
+                me = len(lst)
+                if v < 0:
+                    leaf = ~int(v)
+                    e = ents[off[leaf]:off[leaf + 1]]
+                    lst.append(Leaf(-1, self.n_classes, e[:, 0].astype(np.int32), e[:, 1].astype(np.int32),
+                                    int(sums[leaf])))
+                    return me
+                nd = nodes[v]
+                s = Split(np.int32(nd[0]).view(np.float32), 0, 0, int(nd[1]), int(nd[3]), int(nd[2]), int(nd[4]))
+                lst.append(s)
+                s.left = emit(nd[5])
+                s.right = emit(nd[6])
+                return me
+
+            emit(h["roots"][r, t])
+            trees.append(lst)
+        forests.append(Forest(trees))
+    return forests
+
+
+HyperDepthForests.train = classmethod(_train)
+HyperDepthForests.train.__func__.__doc__ = """Trains the forests of rows [row_from, row_to) (the reference's clamping)
+    from uint8 ims and f32 disps [N, H, W] on one GPU, on the current stream, and returns them as device tables ready
+    for `.eval`.  params: TrainParams; the result is an exact function of the inputs and `seed` (include/ctd_hip.h,
+    ctd_hyperdepth_train_f32).  Raises ValueError on the contract's restrictions, before any launch."""
+HyperDepthForests._from_tables = classmethod(_from_tables)
+HyperDepthForests.to_forests = _to_forests
+
+
+def train_forest(params, ims, disps, n_disp_bins=10, depth_switch=0, n_threads=18, forest_prefix="forest",
+                 row_from=-1, row_to=-1, seed=0):
+    """Drop-in for the reference's hyperdepth.pyx `train_forest`: numpy uint8 ims and f32 disps [N, H, W] in,
+    `<forest_prefix><row>.bin` out for every trained row.  n_threads is accepted and ignored; `seed` keys the
+    generator.  Runs on the current GPU."""
+    ims = np.ascontiguousarray(ims)
+    disps = np.ascontiguousarray(disps)
+    if ims.dtype != np.uint8 or ims.ndim != 3 or disps.dtype != np.float32 or disps.ndim != 3:
+        raise ValueError("ims must be uint8 [N, H, W] and disps float32 [N, H, W]")
+    if ims.shape != disps.shape:
+        raise Exception("ims.shape != disps.shape")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    forests = HyperDepthForests.train(torch.from_numpy(ims).to(dev), torch.from_numpy(disps).to(dev), params,
+                                      n_disp_bins, depth_switch, row_from, row_to, seed, dev)
+    for r, f in enumerate(forests.to_forests()):
+        save_forest(f, "%s%d.bin" % (forest_prefix, forests.row0 + r))
+    return forests

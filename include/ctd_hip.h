@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables, ctd_mesh_bvh_bytes / ctd_mesh_bvh_workspace_bytes / ctd_mesh_bvh_build_f32 / ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables, ctd_hyperdepth_train_count_f32 / ctd_hyperdepth_train_workspace_bytes / ctd_hyperdepth_train_f32 / ctd_hd_train_params / ctd_hd_train_out, ctd_mesh_bvh_bytes / ctd_mesh_bvh_workspace_bytes / ctd_mesh_bvh_build_f32 / ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -611,6 +611,83 @@ typedef struct ctd_hd_tables {
 } ctd_hd_tables;                 /* 88 bytes */
 int ctd_hyperdepth_eval_f32(const ctd_hd_tables* tables, const uint8_t* ims, int N, int H, int W, int row_from,
                             int row_to, int n_disp_bins, float* out, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * HyperDepth random-forest training (additive in ABI version 5).
+ * The reference's trainer (hyperdepth.pyx `train_forest` -> hyperdepth.h `train`: extract_row_samples,
+ * rf/train.h TrainForestQueued / OptimizeSplitFunction / SampleData / Split, HyperdepthSplitEvaluator,
+ * HyperdepthLeafFunction::Create) with its std::random_device / std::mt19937 draws replaced by the counter-based
+ * generator below: the output is an exact function of the inputs and the seed.  It departs from the reference only
+ * where the reference is non-deterministic or would round differently on another machine (the cost, see below).
+ *
+ * Samples of row r: the pairs (n, col), n-major then col, for which d = disps[n][r][col] gives
+ *   cl = (int)trunc((float)((float)col - d) * (float)n_disp_bins)      (f32, no contraction)
+ * with d >= 0 and 0 <= cl < W * n_disp_bins (a NaN d is excluded, as the reference's cvttss2si does on x86; a product
+ * in (-1, 0) gives cl = 0; the upper bound cannot fail for W * n_disp_bins < 2^24 -- the reference would index past
+ * its counts otherwise).
+ * Trees: n_trees per row, each starts from all of the row's samples.  Nodes: heap ids (root 1, children 2i, 2i + 1),
+ * the root at depth 0.  A node of n samples tries to split iff depth < max_tree_depth and n > min_samples_to_split,
+ * otherwise it is a leaf.
+ * Randomness, uint64 wrapping arithmetic:
+ *   mix64(x): x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31
+ *   base = mix64(mix64(mix64(mix64(seed) ^ row) ^ tree) ^ node)     (row = absolute image row, node = heap id)
+ *   draw(slot, m) = ((mix64(base ^ slot) >> 32) * m) >> 32           in [0, m)
+ * Split subset, k' = min(n_test_samples, n): all n samples if n <= n_test_samples, else Floyd: for i in [0, k'):
+ *   j = n - k' + i, t = draw(i, j + 1); choose j if t is chosen already, else t.  Chosen positions in increasing
+ *   order (the reference's std::set).
+ * Candidates: for f in [0, F): h0, w0, h1, w1 = draw(2^40 + 8f + e, 32), e = 0..3 (c0 = c1 = 0: one channel); for j
+ *   in [0, J): threshold = feature of subset element draw(2^41 + f * 2^16 + j, k'); feature = v(h0, w0) - v(h1, w1)
+ *   in f32 with v as in the eval block below (clamped 32 x 32 patch, centre at +16).  Left iff feature < threshold.
+ * Cost on the subset: valid iff both sides hold >= min_samples_for_leaf samples; class = cl / n_disp_bins at
+ *   depth < depth_switch, cl otherwise; with the caller's table X[x] = int64(rint(x * log(x) * 2^32)), X[0] = X[1] = 0,
+ *   cost = X[nL] + X[nR] - sum_c X[cL(c)] - sum_c X[cR(c)]  (int64: n * 2^32 * the reference's normalised weighted
+ *   entropy, exact and independent of summation order).  The best is the valid candidate with the smallest
+ *   (cost, f, j) (the reference's strict <: the first wins ties); none valid -> leaf.  Otherwise all n samples are
+ *   partitioned, order preserved, into left (feature < threshold) and right.
+ * Leaf: dense counts of the fine cl over its samples, n_counts = W * n_disp_bins, sum_counts = n, header n_classes_
+ *   = -1 (Create builds it with the default constructor).  A row without samples gives n_trees single-leaf trees
+ *   with all-zero counts.
+ *
+ * Output: the ctd_hd_tables layout of the eval block (nodes, roots [n_rows][n_trees], leaf_off, leaf_sum, entries with
+ * the non-zero counts only, class-sorted), indices assigned level by level in a deterministic order, so that the
+ * tables can be evaluated without leaving the device.  used[5] (device int64) receives n_nodes, n_leaves, n_entries,
+ * max_depth and an error flag (non-zero: a capacity below the bounds below was passed, or the counts the workspace
+ * was sized for are smaller than the device's own; the tables are then incomplete).  Bounds per tree of a row with
+ * n_r samples (D = max_tree_depth): split nodes <= min(2^D - 1, max(n_r - 1, 0)), leaves <= splits + 1, entries
+ * <= n_r; leaf_off needs cap_leaves + 1 entries.
+ * ctd_hyperdepth_train_count_f32 writes the per-row sample counts (device int64 [row_to - row_from]); the workspace
+ * query and the training call take the same counts in HOST memory (row_counts), copied by the caller.
+ * X is a device int64 table of n_x >= n_test_samples + 1 entries.  The callee never allocates.
+ *
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for NULL pointers, N < 1, H or W < 1 or >= 2^24,
+ * N * H * W >= 2^31, rows outside 0 <= row_from < row_to <= H, n_disp_bins < 1, W * n_disp_bins >= 2^31,
+ * n_trees outside [1, 16], max_tree_depth outside [0, 24], n_test_split_functions outside [0, 2^20),
+ * n_test_thresholds outside [0, 2^16), n_test_samples outside [1, 8192], min_samples_to_split < 0,
+ * min_samples_for_leaf < 1, negative row counts, n_x < n_test_samples + 1, negative capacities;
+ * CTD_ERR_WORKSPACE for a short workspace.
+ * -------------------------------------------------------------------------------------- */
+typedef struct ctd_hd_train_params {
+  int32_t n_trees, max_tree_depth, n_test_split_functions, n_test_thresholds, n_test_samples;
+  int32_t min_samples_to_split, min_samples_for_leaf, depth_switch, n_disp_bins, reserved;
+  uint64_t seed;
+} ctd_hd_train_params;           /* 48 bytes */
+typedef struct ctd_hd_train_out {
+  int32_t* nodes;                /* [cap_nodes][8]     */
+  int32_t* roots;                /* [n_rows][n_trees]  */
+  int64_t* leaf_off;             /* [cap_leaves + 1]   */
+  int32_t* leaf_sum;             /* [cap_leaves]       */
+  int32_t* entries;              /* [cap_entries][2]   */
+  int64_t* used;                 /* [5]                */
+  int64_t cap_nodes, cap_leaves, cap_entries;
+} ctd_hd_train_out;              /* 72 bytes */
+int ctd_hyperdepth_train_count_f32(const float* disps, int N, int H, int W, int row_from, int row_to,
+                                   int n_disp_bins, int64_t* counts, int device, void* stream);
+size_t ctd_hyperdepth_train_workspace_bytes(const ctd_hd_train_params* params, int n_rows, const int64_t* row_counts,
+                                            int64_t cap_leaves);
+int ctd_hyperdepth_train_f32(const ctd_hd_train_params* params, const int64_t* X, int n_x, const uint8_t* ims,
+                             const float* disps, int N, int H, int W, int row_from, int row_to,
+                             const int64_t* row_counts, void* workspace, size_t workspace_bytes,
+                             const ctd_hd_train_out* out, int device, void* stream);
 
 #ifdef __cplusplus
 }
