@@ -74,6 +74,14 @@ SIGNATURES = {
                                                                                           _vp]),
     "ctd_costvol_subpixel_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float, _c_int, _c_int,
                                                                                          _vp]),
+    "ctd_match_validity_f32": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_c_float, _c_int, _vp]),
+    "ctd_xcorrvol_validity_workspace_bytes": (_c_size_t, [_c_int] * 7),
+    "ctd_xcorrvol_validity_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 8 + [_c_float, _vp, _c_size_t,
+                                                                                               _c_int, _vp]),
+    "ctd_costvol_validity_workspace_bytes": (_c_size_t, [_c_int] * 8),
+    "ctd_costvol_validity_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float, _c_int, _c_int,
+                                                                                              _c_float, _vp, _c_size_t,
+                                                                                              _c_int, _vp]),
     "ctd_lcn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_fast_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_datagen_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),

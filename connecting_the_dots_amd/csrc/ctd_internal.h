@@ -131,6 +131,22 @@ int costvol_subpixel_f32(const float* im, const float* pat, long pat_frame_strid
                          uint8_t* refined, int frames, int H, int W, int D, int bs, int type, float eps, int mode,
                          hipStream_t stream);
 
+// match_validity.hip
+struct ValidityLayout {                        // workspace of the *_validity calls (byte offsets; ctd_hip.h documents it)
+  size_t counters, pix_list, col_list, vol, inner, bytes;
+};
+ValidityLayout validity_layout(int frames, int H, int W, int D, size_t inner_bytes);
+bool match_validity_supported(int frames, int H, int W);
+int match_validity_scan_f32(const float* vol, bool maximise, bool fast, const int64_t* idx, uint8_t* flags,
+                            int64_t* idx_r, float* gap, int frames, int D, int H, int W, float min_gap,
+                            unsigned* counters, unsigned* pix_list, unsigned* col_list, hipStream_t stream);
+int match_validity_rescore_f32(int family, const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                               uint8_t* flags, int64_t* idx_r, float* gap, int frames, int H, int W, int D, int bs,
+                               float eps, float min_gap, const unsigned* counters, const unsigned* pix_list,
+                               const unsigned* col_list, hipStream_t stream);
+int match_validity_flags(const int64_t* idx, const int64_t* idx_r, uint8_t* flags, int frames, int H, int W, int lr_tol,
+                         hipStream_t stream);
+
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

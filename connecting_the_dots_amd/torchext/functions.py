@@ -299,14 +299,20 @@ def prepare_pattern(in1, n_frames, n_disps, block_size):
 
 
 def xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume=False, algo=None, rerank_eps=1e-5, prepared=None,
-                    subpixel=None):
+                    subpixel=None, validity=None):
     """Additive: fused NCC volume + argmax over disparity (C == 1).
     in0 [N,1,H,W] | [1,H,W]; in1 [1,H,W] | [N,1,H,W].
     Returns (idx int64, best f32[, volume]); idx == torch.argmax(xcorrvol(...), 0) of the reference.
     `prepared`: a `prepare_pattern` handle of the same `in1`, frame count and shape (fast path only): the pattern half of
     the pre-pass is skipped and the handle's workspace is used.
     subpixel: None (default) | "parabola" | "equiangular": also return (disp f32, refined u8) of
-    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple."""
+    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple.
+    validity: None (default) | dict(lr_tol=..., min_gap=...): also return (flags, idx_r, gap) of
+    `xcorrvol_validity(in0, in1, idx, ..., algo=algo)` at the end of the tuple (after the sub-pixel outputs)."""
+    if validity is not None:
+        kw = _validity_kwargs(validity, "xcorrvol_argmax")
+        out = xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume, algo, rerank_eps, prepared, subpixel)
+        return tuple(out) + xcorrvol_validity(in0, in1, out[0], n_disps, block_size, algo=algo, **kw)
     if subpixel is not None:
         _subpixel_mode(subpixel, "xcorrvol_argmax")
         out = xcorrvol_argmax(in0, in1, n_disps, block_size, return_volume, algo, rerank_eps, prepared)
@@ -720,7 +726,7 @@ def costvol(im, pattern, n_disps, block_size, type='sad', eps=0.1, algo=None):
 
 
 def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1, rerank_rel=1e-5, return_rescored=False,
-                   subpixel=None):
+                   subpixel=None, validity=None):
     """Additive: the disparity of least SAD / MSE / soft-census block cost without the cost volume.
     im [N,H,W] | [H,W] f32, pattern [H,W] | [N,H,W] (as `costvol`) -> (idx int64, best f32), each [N,H,W] | [H,W].
     idx equals torch.argmin(costvol(..., algo="exact"), 1) bit for bit (first index on ties): the fast volume kernel
@@ -733,7 +739,13 @@ def costvol_argmin(im, pattern, n_disps, block_size, type='census_sad', eps=0.1,
     Block sizes the kernels do not cover (odd, > 9) fall back to costvol(algo="exact") + torch.argmin (all pixels then
     count as re-scored).
     subpixel: None (default) | "equiangular" | "parabola": also return (disp, refined) of
-    `costvol_subpixel(im, pattern, idx, ...)` at the end of the tuple (no accuracy gain for the census types)."""
+    `costvol_subpixel(im, pattern, idx, ...)` at the end of the tuple (no accuracy gain for the census types).
+    validity: None (default) | dict(lr_tol=..., min_gap=...): also return (flags, idx_r, gap) of
+    `costvol_validity(im, pattern, idx, ...)` at the end of the tuple (after the sub-pixel outputs)."""
+    if validity is not None:
+        kw = _validity_kwargs(validity, "costvol_argmin")
+        out = costvol_argmin(im, pattern, n_disps, block_size, type, eps, rerank_rel, return_rescored, subpixel)
+        return tuple(out) + costvol_validity(im, pattern, out[0], n_disps, block_size, type, eps, **kw)
     if subpixel is not None:
         _subpixel_mode(subpixel, "costvol_argmin")
         out = costvol_argmin(im, pattern, n_disps, block_size, type, eps, rerank_rel, return_rescored)
@@ -888,6 +900,161 @@ def costvol_subpixel(im, pattern, idx, n_disps, block_size, type='census_sad', e
 
 xcorrvol_subpixel.__doc__ += _SUBPIXEL_RULE
 costvol_subpixel.__doc__ += _SUBPIXEL_RULE
+
+
+# --------------------------------------------------------------------------------------
+# Match validity: left-right consistency and uniqueness (additive; include/ctd_hip.h states the rule word for word)
+# --------------------------------------------------------------------------------------
+VALID_IN_PATTERN, VALID_LR_OK, VALID_UNIQUE = 1, 2, 4
+
+_VALIDITY_RULE = """
+    The rule (include/ctd_hip.h), on the reference-order volume V (NCC: xcorrvol(algo="exact"), higher is better; costs:
+    costvol(algo="exact"), lower is better), d0 = idx:
+      idx_r[f,h,x] = first index of the best V[f,d,h,x+d] over d in [0, min(D, W-x))     (the pattern-side match)
+      gap[f,h,w]   = s1 - s2 (NCC) | s2 - s1 (costs), s1 = V[d0], s2 = the best V[d] over |d - d0| >= 2; +inf when no
+                     such d exists, NaN when idx is outside [0, D)
+      flags bit 0 IN_PATTERN: 0 <= idx < D and w - idx >= 0;  bit 1 LR_OK: bit 0 and |idx_r[f,h,w-idx] - idx| <= lr_tol;
+            bit 2 UNIQUE: 0 <= idx < D and gap > min_gap;  valid = (flags == 7).
+    flags and idx_r are exact with either algo; gap is exact with algo="exact" and on re-scored pixels, otherwise within
+    1e-5 (|s1| + |s2|) + 2e-6."""
+
+
+def _validity_params(lr_tol, min_gap, who):
+    if isinstance(lr_tol, bool) or int(lr_tol) != lr_tol or int(lr_tol) < 0:
+        raise RuntimeError("%s: lr_tol must be an int >= 0" % who)
+    min_gap = float(min_gap)
+    if not min_gap >= 0.0:
+        raise RuntimeError("%s: min_gap must be a number >= 0" % who)
+    return int(lr_tol), min_gap
+
+
+def _validity_outputs(idx):
+    dev = idx.device
+    return (torch.empty(idx.shape, dtype=torch.uint8, device=dev), torch.empty(idx.shape, dtype=torch.int64, device=dev),
+            torch.empty(idx.shape, dtype=torch.float32, device=dev))
+
+
+def _validity_rescored(ws, P, dev):
+    """(sorted flat indices of the re-scored pixels, of the re-scored pattern columns) from the workspace (ctd_hip.h)"""
+    n = ws[:8].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    n_pix, n_col = int(n[0]), int(n[1])
+    off = (256 + 4 * P + 255) // 256 * 256
+    pix = (ws[256:256 + 4 * n_pix].view(torch.int32).to(torch.int64) & 0xFFFFFFFF).sort()[0]
+    col = (ws[off:off + 4 * n_col].view(torch.int32).to(torch.int64) & 0xFFFFFFFF).sort()[0]
+    return pix, col
+
+
+def match_validity(vol, idx, maximise, lr_tol=1, min_gap=0.0):
+    """Additive: (flags u8, idx_r int64, gap f32), each shaped as idx, of a materialised volume taken as exact.
+    vol [N,D,H,W] | [D,H,W] f32, idx int64 [N,H,W] | [H,W] (any index); maximise: True for scores (NCC), False for costs."""
+    _check(vol, "vol", (torch.float32,))
+    _check(idx, "idx", (torch.int64,))
+    lr_tol, min_gap = _validity_params(lr_tol, min_gap, "match_validity")
+    squeeze = vol.dim() == 3
+    v = vol.unsqueeze(0) if squeeze else vol
+    if v.dim() != 4:
+        raise RuntimeError("match_validity expects vol [N,D,H,W] or [D,H,W]")
+    dev = _same_device(v, idx)
+    N, D, H, W = v.shape
+    if tuple(idx.shape) != ((H, W) if squeeze else (N, H, W)):
+        raise RuntimeError("match_validity: idx must be shaped [N,H,W] (or [H,W]) like the volume without its D axis")
+    flags, idx_r, gap = _validity_outputs(idx)
+    st = _lib.lib().ctd_match_validity_f32(_ptr(v), 1 if maximise else 0, _ptr(idx), _ptr(flags), _ptr(idx_r), _ptr(gap),
+                                           N, D, H, W, lr_tol, min_gap, dev.index, _stream(dev))
+    _lib.check(st, "match_validity")
+    return flags, idx_r, gap
+
+
+def xcorrvol_validity(in0, in1, idx, n_disps, block_size, lr_tol=1, min_gap=0.0, algo=None, return_rescored=False):
+    """Additive: left-right consistency and uniqueness of NCC matcher indices -> (flags u8, idx_r int64, gap f32), each
+    shaped as idx.  in0 [N,C,H,W] | [C,H,W] and in1 [C,H,W] | [N,C,H,W] as `xcorrvol_batch` / `xcorrvol_argmax` take them,
+    idx int64 [N,H,W] | [H,W] as `xcorrvol_argmax` returns it (any index).  The volume is computed into a workspace
+    (N * D * H * W floats) and read once.
+    algo: 'fast' (default) | 'exact'; shapes the fast NCC path does not cover here (C > 1, block sizes other than
+    3/5/7/9, D > 512) take 'exact'.
+    return_rescored: also return (pixels, columns), the sorted int64 flat indices of the pixels and pattern columns the
+    fast path settled by exact re-scoring (both empty with 'exact')."""
+    _check(in0, "in0", (torch.float32,))
+    _check(in1, "in1", (torch.float32,))
+    _check(idx, "idx", (torch.int64,))
+    lr_tol, min_gap = _validity_params(lr_tol, min_gap, "xcorrvol_validity")
+    squeeze = in0.dim() == 3
+    a0 = in0.unsqueeze(0) if squeeze else in0
+    if a0.dim() != 4 or in1.dim() not in (3, 4):
+        raise RuntimeError("xcorrvol_validity expects in0 [N,C,H,W] or [C,H,W] and in1 [C,H,W] or [N,C,H,W]")
+    dev = _same_device(a0, in1, idx)
+    N, C, H, W = a0.shape
+    if tuple(in1.shape[-3:]) != (C, H, W) or (in1.dim() == 4 and in1.shape[0] != N):
+        raise RuntimeError("xcorrvol_validity: in1 does not match in0")
+    if tuple(idx.shape) != ((H, W) if squeeze else (N, H, W)):
+        raise RuntimeError("xcorrvol_validity: idx must be shaped as xcorrvol_argmax returns it")
+    D, bs = int(n_disps), int(block_size)
+    algo = algo or _default_algo()
+    if algo not in _ALGOS:
+        raise RuntimeError("unknown algo %r" % (algo,))
+    if algo == "fast" and not (C == 1 and _ncc_fast_covers(a0.dtype, D, bs)):
+        algo = "exact"
+    a = _ALGOS[algo]
+    stride1 = 0 if in1.dim() == 3 else C * H * W
+    flags, idx_r, gap = _validity_outputs(idx)
+    L = _lib.lib()
+    ws = _workspace(L.ctd_xcorrvol_validity_workspace_bytes(N, C, H, W, D, bs, a), dev)
+    st = L.ctd_xcorrvol_validity_f32(_ptr(a0), _ptr(in1), stride1, _ptr(idx), _ptr(flags), _ptr(idx_r), _ptr(gap), N, C, H,
+                                     W, D, bs, a, lr_tol, min_gap, _ptr(ws), ws.numel(), dev.index, _stream(dev))
+    _lib.check(st, "xcorrvol_validity")
+    if return_rescored:
+        return (flags, idx_r, gap) + _validity_rescored(ws, N * H * W, dev)
+    return flags, idx_r, gap
+
+
+def costvol_validity(im, pattern, idx, n_disps, block_size, type='census_sad', eps=0.1, lr_tol=1, min_gap=0.0, algo=None,
+                     return_rescored=False):
+    """Additive: left-right consistency and uniqueness of cost-volume indices -> (flags u8, idx_r int64, gap f32), each
+    shaped as idx.  im [N,H,W] | [H,W] and pattern [H,W] | [N,H,W] as `costvol_argmin` takes them, idx int64 shaped as it
+    returns it (any index).  The volume is computed into a workspace (N * D * H * W floats) and read once.
+    algo: 'fast' (default, or env CTD_PHOTO_ALGO) | 'exact'; block sizes other than 3/5/7/9 take 'exact'.
+    return_rescored: as `xcorrvol_validity`."""
+    _check(im, "im", (torch.float32,))
+    _check(pattern, "pattern", (torch.float32,))
+    _check(idx, "idx", (torch.int64,))
+    lr_tol, min_gap = _validity_params(lr_tol, min_gap, "costvol_validity")
+    type = type.lower()
+    if type not in _PHOTO_TYPES:
+        raise RuntimeError("costvol_validity: invalid loss type %r" % (type,))
+    squeeze = im.dim() == 2
+    a = im.unsqueeze(0) if squeeze else im
+    if a.dim() != 3 or pattern.dim() not in (2, 3) or tuple(pattern.shape[-2:]) != tuple(a.shape[-2:]):
+        raise RuntimeError("costvol_validity expects im [N,H,W] or [H,W] and pattern [H,W] or [N,H,W]")
+    dev = _same_device(a, pattern, idx)
+    N, H, W = a.shape
+    if pattern.dim() == 3 and pattern.shape[0] != N:
+        raise RuntimeError("costvol_validity: pattern batch does not match im")
+    if tuple(idx.shape) != tuple(im.shape):
+        raise RuntimeError("costvol_validity: idx must be shaped as costvol_argmin returns it")
+    D, bs, ty = int(n_disps), int(block_size), _PHOTO_TYPES[type]
+    fast = 1 if _photo_fast(a, bs, algo) else 0
+    stride = 0 if pattern.dim() == 2 else H * W
+    flags, idx_r, gap = _validity_outputs(idx)
+    L = _lib.lib()
+    ws = _workspace(L.ctd_costvol_validity_workspace_bytes(N, H, W, D, bs, ty, fast, 1 if stride else 0), dev)
+    st = L.ctd_costvol_validity_f32(_ptr(a), _ptr(pattern), stride, _ptr(idx), _ptr(flags), _ptr(idx_r), _ptr(gap), N, H, W,
+                                    D, bs, ty, float(eps), fast, lr_tol, min_gap, _ptr(ws), ws.numel(), dev.index,
+                                    _stream(dev))
+    _lib.check(st, "costvol_validity")
+    if return_rescored:
+        return (flags, idx_r, gap) + _validity_rescored(ws, N * H * W, dev)
+    return flags, idx_r, gap
+
+
+def _validity_kwargs(validity, who):
+    if not isinstance(validity, dict) or not set(validity) <= {"lr_tol", "min_gap"}:
+        raise RuntimeError("%s: validity must be None or a dict with the keys lr_tol and / or min_gap" % who)
+    return validity
+
+
+match_validity.__doc__ += _VALIDITY_RULE
+xcorrvol_validity.__doc__ += _VALIDITY_RULE
+costvol_validity.__doc__ += _VALIDITY_RULE
 
 
 # --------------------------------------------------------------------------------------

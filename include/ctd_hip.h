@@ -38,7 +38,7 @@ enum ctd_status {
   CTD_ERR_HIP = 1000           /* 1000 + hipError_t of the failing runtime call           */
 };
 
-int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables, ctd_hyperdepth_train_count_f32 / ctd_hyperdepth_train_workspace_bytes / ctd_hyperdepth_train_f32 / ctd_hd_train_params / ctd_hd_train_out, ctd_mesh_bvh_bytes / ctd_mesh_bvh_workspace_bytes / ctd_mesh_bvh_build_f32 / ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32 -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
+int ctd_version(void);                       /* ABI version, currently 5 (5, additive since: ctd_syn_finish_f32 / ctd_augment_f32 / ctd_salt_pepper_f32, ctd_costvol_argmin_f32 / ctd_costvol_argmin_workspace_bytes, ctd_xcorrvol_subpixel_f32 / ctd_xcorrvol_subpixel_workspace_bytes / ctd_costvol_subpixel_f32, ctd_hyperdepth_eval_f32 / ctd_hd_tables, ctd_hyperdepth_train_count_f32 / ctd_hyperdepth_train_workspace_bytes / ctd_hyperdepth_train_f32 / ctd_hd_train_params / ctd_hd_train_out, ctd_mesh_bvh_bytes / ctd_mesh_bvh_workspace_bytes / ctd_mesh_bvh_build_f32 / ctd_render_mesh_proj_bvh_f32 / ctd_render_mesh_bvh_f32, ctd_match_validity_f32 / ctd_xcorrvol_validity_f32 / ctd_xcorrvol_validity_workspace_bytes / ctd_costvol_validity_f32 / ctd_costvol_validity_workspace_bytes -- no existing signature changed; 5: + ctd_lcn_xcorrvol_argmax_f32 / ctd_lcn_xcorrvol_supported; 4: ctd_costvol_fast_f32 takes a workspace, ctd_costvol_workspace_bytes; 2: ranked argmax inside the all-D volume kernel, its workspace is ctd_xcorrvol_argmax_workspace_bytes(); 3: + ctd_xcorrvol_pattern_prepare_f32 / CTD_PATTERN_PREPARED, ctd_geometric_sym_fwd_f32) */
 const char* ctd_status_string(int status);
 
 /* (Bench instrumentation -- per-kernel device timing of the volume kernel -- is declared in ctd_hip_bench.h: it is not
@@ -254,6 +254,73 @@ int ctd_xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame
 int ctd_costvol_subpixel_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
                              float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int type,
                              float eps, int mode, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * Match validity (additive in ABI version 5): which disparities of a winner-takes-all matcher can be trusted -- the
+ * left-right consistency check and the uniqueness check of classical stereo / structured-light matchers.
+ *
+ * Definitions.  Let V[f][d][h][w] be the reference-order volume: for NCC the volume of ctd_xcorrvol_f32(CTD_NCC_EXACT),
+ * higher is better; for the costs the volume of ctd_costvol_f32, lower is better.  Below, "better" and "best" follow
+ * the family.  Inputs are assumed finite.  idx is the int64 [frames][H][W] index tensor the caller passes, normally the
+ * matcher's output; any index is accepted, as in the sub-pixel ops.
+ *   1. Pattern-side match idx_r[f][h][x] (int64 [frames][H][W], x = pattern column): the first index of the best
+ *      V[f][d][h][x + d] over d in [0, min(D, W - x)) -- the disparity at which pattern column x is best explained by
+ *      the frame, by the same scores and the same tie rule as the frame-side argmax.  The range is never empty
+ *      (d = 0 is always in it).
+ *   2. gap[f][h][w] (f32).  With d0 = idx, s1 = V[d0] and s2 = the best V[d] over |d - d0| >= 2:
+ *      NCC: gap = s1 - s2;  costs: gap = s2 - s1;  both one f32 subtraction.  gap = +inf when no such d exists,
+ *      gap = NaN when idx is outside [0, D).
+ *   3. flags[f][h][w] (uint8 bit field):
+ *      bit 0 IN_PATTERN: 0 <= idx < D and x = w - idx >= 0 (such a match does not rest on the replicated left border,
+ *            ext.h:152-154);
+ *      bit 1 LR_OK: bit 0 holds and |idx_r[f][h][x] - idx| <= lr_tol (lr_tol an int >= 0);
+ *      bit 2 UNIQUE: 0 <= idx < D and gap > min_gap (an f32 compare; +inf passes; min_gap an f32 >= 0).
+ *      valid = (flags == 7).
+ *
+ * ctd_match_validity_f32: the three outputs of a caller-supplied volume vol [frames][D][H][W], taken as exact (it IS V).
+ *   maximise != 0: higher is better (NCC), 0: lower is better (costs).  No workspace.  idx, flags, idx_r and gap must
+ *   not overlap.
+ * ctd_xcorrvol_validity_f32 / ctd_costvol_validity_f32: compute the volume into the workspace (ctd_xcorrvol_f32 with
+ *   `algo`; ctd_costvol_f32 for algo = CTD_NCC_EXACT, ctd_costvol_fast_f32 for CTD_NCC_FAST -- the same 0 / 1), then
+ *   the three outputs.  What is exact: idx_r and flags are those of V bit for bit with either algo.  gap equals V's gap
+ *   bit for bit with CTD_NCC_EXACT; with CTD_NCC_FAST it is within 1e-5 (|s1| + |s2|) + 2e-6 of it (the sum of the fast
+ *   bounds of its operands) and bit-exact on the re-scored pixels.
+ *   How CTD_NCC_FAST keeps decisions exact: a decision taken on fast scores is accepted only where the fast bound
+ *   |fast - exact| <= 1e-5 |exact| + 1e-6 proves it -- pattern side: best and runner-up of the diagonal (the runner-up
+ *   anywhere) farther apart than both bounds; uniqueness: |gap_fast - min_gap| larger than both bounds plus the
+ *   rounding of the subtraction (csrc/match_validity.hip has the derivation).  Every other pixel / pattern column,
+ *   exact ties included, goes on a list; all its D scores are evaluated again in the reference order and the decision
+ *   is taken on them.  LR_OK is taken after the pattern-side list is resolved.  Each list has room for every pixel /
+ *   column.
+ *   Arguments as ctd_xcorrvol_f32 (in1_frame_stride 0 or C * H * W) / ctd_costvol_fast_f32 (pattern_frame_stride 0 or
+ *   H * W).
+ * Workspace: *_validity_workspace_bytes() bytes, 256-byte aligned.  With P = frames * H * W:
+ *   bytes [0, 4): u32 number of re-scored pixels, bytes [4, 8): u32 number of re-scored pattern columns (both 0 with
+ *   CTD_NCC_EXACT); from byte 256: the re-scored pixels' flat indices f * H * W + h * W + w (u32, order unspecified);
+ *   from byte 256 + 4 P rounded up to a multiple of 256: the re-scored columns' flat indices f * H * W + h * W + x;
+ *   then the volume and the volume kernels' scratch.
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for lr_tol < 0, a negative or NaN min_gap, an algo / type outside its
+ *   values, a pattern stride other than the two above, bad sizes (D * H * W >= 2^31 included) or a NULL pointer;
+ *   CTD_ERR_UNSUPPORTED for H or frames > 65535, frames * H * W >= 2^32, CTD_NCC_FAST with C > 1, D > 512 or a block
+ *   size outside 3/5/7/9 (use CTD_NCC_EXACT), and the exact cost volume with frames * D > 65535; CTD_ERR_WORKSPACE for a
+ *   NULL, short or misaligned workspace.  frames == 0 is CTD_OK.  The workspace queries return 0 for all of these.
+ * -------------------------------------------------------------------------------------- */
+#define CTD_VALID_IN_PATTERN 1
+#define CTD_VALID_LR_OK 2
+#define CTD_VALID_UNIQUE 4
+int ctd_match_validity_f32(const float* vol, int maximise, const int64_t* idx, uint8_t* flags, int64_t* idx_r, float* gap,
+                           int frames, int D, int H, int W, int lr_tol, float min_gap, int device, void* stream);
+size_t ctd_xcorrvol_validity_workspace_bytes(int frames, int C, int H, int W, int D, int block_size, int algo);
+int ctd_xcorrvol_validity_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                              uint8_t* flags, int64_t* idx_r, float* gap, int frames, int C, int H, int W, int D,
+                              int block_size, int algo, int lr_tol, float min_gap, void* workspace,
+                              size_t workspace_bytes, int device, void* stream);
+size_t ctd_costvol_validity_workspace_bytes(int frames, int H, int W, int D, int block_size, int type, int algo,
+                                            int per_frame_pattern);
+int ctd_costvol_validity_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
+                             uint8_t* flags, int64_t* idx_r, float* gap, int frames, int H, int W, int D, int block_size,
+                             int type, float eps, int algo, int lr_tol, float min_gap, void* workspace,
+                             size_t workspace_bytes, int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
