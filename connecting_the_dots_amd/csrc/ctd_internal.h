@@ -20,7 +20,7 @@ int ncc_exact_argmax_f32(const float* in0, const float* in1, long in1_frame_stri
                          size_t workspace_bytes, hipStream_t stream);
 int argmax_disp_f32(const float* vol, int64_t* idx, float* best, int frames, int D, int H, int W, hipStream_t stream);
 
-// ncc_fast.hip
+// ncc_fast.hip (entry points of the fast NCC path; its kernel files share ctd_ncc_fast.h)
 // Buffers of the in-kernel ranking (all inside the caller's workspace, laid out by ncc_fast_f32).
 struct RankPlan {
   float eps;                  // in: re-ranking margin requested by the caller
@@ -60,7 +60,7 @@ int ncc_fast_prepare_pattern_f32(const float* in1, long in1_frame_stride, int fr
 int ncc_fast_fixup_ranked(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int H, int W,
                           int D, int bs, void* workspace, const RankPlan& rank, const float* best, hipStream_t stream);
 
-// separable block SAD / MSE cost volume through the all-D pipeline (block 9, W % 4 == 0); workspace = padded operand planes
+// costvol_sep.hip: separable block SAD / MSE cost volume through the all-D pipeline (block 9, W % 4 == 0); workspace = padded operand planes
 bool costvol_sep_supported(int H, int W, int D, int bs, int type);
 size_t costvol_sep_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern);
 int costvol_sep_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W, int D,
@@ -73,7 +73,7 @@ int argmax_rerank_f32(const float* vol, const float* in0, const float* in1, long
 int rank_tail_f32(const RankPlan& rp, float* vol, const float* in0, const float* in1, long in1_frame_stride,
                   int64_t* idx, float* best, int frames, int D, int H, int W, int bs, hipStream_t stream);
 
-// ncc_fast.hip: compute units of the current device (cached)
+// ncc_alld.hip: compute units of the current device (cached)
 int device_cu_count();
 
 // photometric.hip

@@ -1,4 +1,4 @@
-// ctd_prepass.h -- what the kernels that produce the matcher's frame-side window statistics share (ncc_fast.hip:
+// ctd_prepass.h -- what the kernels that produce the matcher's frame-side window statistics share (ncc_prepass.hip:
 // ncc_prepass_kernel; lcn_stream.hip: the fused LCN + statistics kernel).
 #pragma once
 #include "ctd_common.h"

@@ -1,11 +1,11 @@
-// ctd_rank.h -- device helpers shared by the passes of the ranked fast argmax (ncc_fast.hip, argmax_rerank.hip).
+// ctd_rank.h -- device helpers shared by the passes of the ranked fast argmax (ncc_alld.hip, ncc_fixup.hip, argmax_rerank.hip).
 #pragma once
 #include "ctd_common.h"
 
 namespace ctd {
 
 // Margin inside which two scores count as tied for the exact re-scoring: the caller's eps plus the resolution of two
-// keys of the in-kernel ranking (fixed point, 2^-21 = 4.8e-7 absolute each way, ncc_fast.hip).  The all-D kernel and the
+// keys of the in-kernel ranking (fixed point, 2^-21 = 4.8e-7 absolute each way, ncc_alld.hip).  The all-D kernel and the
 // fix-up check use this one expression.
 __device__ inline float rank_margin(float eps, float top) {
   (void)top;

@@ -1,4 +1,4 @@
-// ctd_tail.h -- device roles shared by the tail passes of the fast NCC path (ncc_fast.hip, argmax_rerank.hip).
+// ctd_tail.h -- device roles shared by the tail passes of the fast NCC path (ncc_fixup.hip, argmax_rerank.hip).
 #pragma once
 #include "ctd_common.h"
 

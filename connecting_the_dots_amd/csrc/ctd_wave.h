@@ -1,4 +1,4 @@
-// ctd_wave.h -- wavefront-level helpers of the loader / consumer kernels (ncc_fast.hip, lcn_stream.hip): LDS-DMA, counted
+// ctd_wave.h -- wavefront-level helpers of the loader / consumer kernels (ncc_tiles.hip, ncc_t256.hip, ncc_alld.hip, lcn_stream.hip): LDS-DMA, counted
 // waits, the raw workgroup barrier.
 #pragma once
 #include "ctd_common.h"

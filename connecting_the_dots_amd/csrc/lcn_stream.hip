@@ -1,7 +1,7 @@
 // lcn_stream.hip -- LCN of the frames and the window statistics of the matcher's pre-pass in ONE streaming kernel.
 //
 // Replaces, for the frames of a fused call (ctd_lcn_xcorrvol_argmax_f32), the two LDS-tiled launches lcn_kernel /
-// lcn_fast_kernel (lcn.hip; LCN.tforward, model/networks.py:507-533) and ncc_prepass_kernel (ncc_fast.hip; the window
+// lcn_fast_kernel (lcn.hip; LCN.tforward, model/networks.py:507-533) and ncc_prepass_kernel (ncc_prepass.hip; the window
 // mean / deviation of XCorrVolFunctor, torchext/ext/ext.h:143-181, hoisted out of the disparity loop).  Both of those
 // are tiles with two barriers and a halo of 10 / 8 pixels each way, and both live on occupancy (docs/history.md);
 // here a workgroup owns a strip of 256 columns (lane = 4 adjacent columns: 16-byte loads and stores) and marches down
@@ -10,7 +10,7 @@
 // pipeline stages (LCN | statistics, one row apart) and a LOADER that streams the raw rows global -> LDS (LDS-DMA,
 // kLsPF rows ahead) and is the only one that ever waits for a load: on gfx950 loads and stores retire in order on one
 // counter, so a wavefront that did both would wait for its newest stores every row (the same split as the volume
-// kernels of ncc_fast.hip); the three meet at one s_barrier per row.
+// kernels of ncc_tiles.hip / ncc_alld.hip); the three meet at one s_barrier per row.
 //   raw row u  --vertical 11-row sums V (per column)-->  horizontal 11-column sums (DPP wave shifts)
 //              --> y = (x - avg) / std of row u - 5 --> stored (LCN output + the matcher's padded copy)
 //              --> vertical 9-row sums of y, y^2 as 3 + 3 + 3 (no running sum: every window is a fresh <= 4-level sum)

@@ -2,7 +2,7 @@
 NCC path's listing rule is stated in, a classifier of every NCC output against that rule, and trap frames that put
 windows next to each of its thresholds (and cost-volume / photometric pairs next to the census-SAD sign decision).
 
-Listing rule (ncc_fast.hip: ncc_prepass_kernel; constants in ctd_prepass.h).  For every window of every image (frame
+Listing rule (ncc_prepass.hip: ncc_prepass_kernel; constants in ctd_prepass.h).  For every window of every image (frame
 f, channel c; pattern channel c) with n = bs^2 samples, mean m and sum of squared deviations V:
     cval   = f32( f64 sum of the window centred at (H/2, W/2), clamped / n )      one constant per image
     F - 1  = n (m - cval)^2 / V

@@ -1,6 +1,6 @@
 """The fast matchers' error bounds, tested where they are stated, on adversarial frames and against float64.
 
-NCC (ncc_fast.hip): the pre-pass lists every window whose outputs the fast kernel cannot deliver within tolerance, the
+NCC (ncc_fast.hip and its kernel files): the pre-pass lists every window whose outputs the fast kernel cannot deliver within tolerance, the
 fix-up pass recomputes those in the reference's order, and every other output is trusted to |fast - exact| <= 1e-5
 |exact| + 1e-6 (C > 1: 1e-5 sum_c |exact_c| + C 1e-6), from the error model |fast - exact| <~ 7 * 2^-24 * sum_c
 sqrt(Fa Fb), which kFlagRatio = 1.39 keeps within that bound.  tests/matcher_traps.py restates
@@ -26,7 +26,7 @@ from tests.util import assert_close
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-MODEL_C = 7.0                          # the error model's constant (ncc_fast.hip, above ncc_fixup_kernel)
+MODEL_C = 7.0                          # the error model's constant (ncc_fixup.hip, above ncc_fixup_kernel)
 
 NCC_SHAPES = T.NCC_SHAPES
 NCC_CASES = [(name, 1) + s for name in T.NCC_GENERATORS for s in NCC_SHAPES]
@@ -58,7 +58,7 @@ def _frames(name, C, bs, H, W):
 def test_ncc_fast_volume_bounds(te, name, C, bs, H, W, D):
     """(a) listed outputs carry the exact kernel's bits; (b) unlisted ones are within the contract of `_within`; (c)
     guard outputs do one or the other; (d) against float64 truth t, unlisted outputs meet the error model
-    (ncc_fast.hip, above ncc_fixup_kernel):
+    (ncc_fixup.hip, above ncc_fixup_kernel):
         |fast - t| <= |exact - t| + 7 * 2^-24 * sum_c sqrt(Fa Fb) + sum_c |t_c| * 1e-8 / (sa sb)
     the last term being the reference denominator's 1e-8, a relative change of each channel's NCC t_c that the fast
     path's reciprocal deviations leave out (kDevFloor bounds it)"""

@@ -1,4 +1,4 @@
-"""GPU parity of the in-kernel ranking of the fast NCC path (ncc_fast.hip all-D kernel -> fix-up -> tail kernel):
+"""GPU parity of the in-kernel ranking of the fast NCC path (ncc_alld.hip all-D kernel -> fix-up -> tail kernel):
 indices must equal torch.argmax of the reference-order volume bit for bit, with the volume
 materialised (return_volume=True) and without one (volume-free).  The checker is the reference-order HIP kernel
 (`algo='exact'`), itself pinned bit for bit to the reference's goldens in test_xcorrvol_gpu.py, and the CPU oracle

@@ -15,7 +15,7 @@
 //   rows2304    one dword per lane, 256 B per wave-instruction, random 2,304-B rows of the table (the guide's row)
 //   copy16      float4 copy, bytes = read + written (the guide's 6.29 TB/s "float4 copy" row)
 //   volume      the NCC volume kernel's own epilogue pattern: a workgroup owns `waves` x 2 disparity planes x a band of
-//               rows x 256 columns and writes one 1 KB row segment per plane and row (ncc_fast.hip, t256 / all-D kernels)
+//               rows x 256 columns and writes one 1 KB row segment per plane and row (ncc_t256.hip / ncc_alld.hip kernels)
 #include <hip/hip_runtime.h>
 #include <chrono>
 
