@@ -82,6 +82,9 @@ SIGNATURES = {
     "ctd_costvol_validity_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float, _c_int, _c_int,
                                                                                               _c_float, _vp, _c_size_t,
                                                                                               _c_int, _vp]),
+    "ctd_sgm_workspace_bytes": (_c_size_t, [_c_int] * 6),
+    "ctd_sgm_aggregate_f32": (_c_int, [_vp, _c_int, _c_float, _c_float, _c_int, _vp, _vp, _vp] + [_c_int] * 4 +
+                              [_vp, _c_size_t, _c_int, _vp]),
     "ctd_lcn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_fast_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_datagen_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),

@@ -592,6 +592,33 @@ int ctd_costvol_validity_f32(const float* im, const float* pattern, long pattern
                          block_size, eps, lr_tol, min_gap, hs);
 }
 
+// ---- semi-global aggregation (sgm.hip) ----
+static bool sgm_args_ok(int frames, int D, int H, int W, int paths, float p1, float p2) {
+  if (frames <= 0 || D <= 0 || H <= 0 || W <= 0 || (paths != 4 && paths != 8)) return false;
+  if ((double)frames * D * H * W >= 2147483648.0) return false;
+  return p1 >= 0.f && p2 >= p1 && p2 <= 3.402823466e38f;                                       // (a NaN fails >=)
+}
+
+size_t ctd_sgm_workspace_bytes(int frames, int D, int H, int W, int paths, int want_volume) {
+  if (!sgm_args_ok(frames, D, H, W, paths, 0.f, 0.f) || !sgm_supported(frames, D, H, W) || want_volume) return 0;
+  return sizeof(float) * (size_t)frames * D * H * W;
+}
+
+int ctd_sgm_aggregate_f32(const float* vol, int maximise, float p1, float p2, int paths, float* S_out, int64_t* idx,
+                          float* best, int frames, int D, int H, int W, void* workspace, size_t workspace_bytes,
+                          int device, void* stream) {
+  if (!sgm_args_ok(frames, D, H, W, paths, p1, p2)) return CTD_ERR_INVALID_ARG;
+  if (!vol || !idx || !best) return CTD_ERR_INVALID_ARG;
+  if (!sgm_supported(frames, D, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!S_out && (!workspace || workspace_bytes < ctd_sgm_workspace_bytes(frames, D, H, W, paths, 0) ||
+                 ((uintptr_t)workspace & 15)))
+    return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return sgm_aggregate_f32(vol, maximise != 0, p1, p2, paths, S_out ? S_out : (float*)workspace, idx, best, frames, D, H, W,
+                           (hipStream_t)stream);
+}
+
 int ctd_disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float baseline_focal, int device, void* stream) {
   if (n < 0) return CTD_ERR_INVALID_ARG;
   if (n == 0) return CTD_OK;

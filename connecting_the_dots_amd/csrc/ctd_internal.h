@@ -147,6 +147,11 @@ int match_validity_rescore_f32(int family, const float* in0, const float* in1, l
 int match_validity_flags(const int64_t* idx, const int64_t* idx_r, uint8_t* flags, int frames, int H, int W, int lr_tol,
                          hipStream_t stream);
 
+// sgm.hip
+bool sgm_supported(int frames, int D, int H, int W);
+int sgm_aggregate_f32(const float* vol, bool maximise, float p1, float p2, int paths, float* S, int64_t* idx, float* best,
+                      int frames, int D, int H, int W, hipStream_t stream);
+
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

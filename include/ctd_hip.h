@@ -323,6 +323,39 @@ int ctd_costvol_validity_f32(const float* im, const float* pattern, long pattern
                              size_t workspace_bytes, int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
+ * Semi-global cost aggregation (additive in ABI version 5): Hirschmueller's SGM path aggregation over a materialised
+ * volume, the step between "cost volume" and "argmin" that lets a pixel's choice be informed by its neighbours.
+ *
+ * Definition (f32 throughout; only add, sub and min, so the result is defined bit for bit).  The input is
+ * vol [frames][D][H][W].  C = vol when maximise == 0 (costs, lower is better), C = -vol otherwise (scores; the negation is
+ * exact).  A path direction is a step (dy, dx); the predecessor of pixel p = (y, x) is q = (y - dy, x - dx).
+ *   q outside the image:  L(p,d) = C(p,d)
+ *   otherwise:            m = min_k L(q,k)
+ *                         t = min(L(q,d), m + P2, L(q,d-1) + P1 [if d >= 1], L(q,d+1) + P1 [if d + 1 < D])
+ *                         L(p,d) = C(p,d) + (t - m)                                   in exactly that association
+ * Directions, as (dy, dx): right (0,+1), left (0,-1), down (+1,0), down-right (+1,+1), down-left (+1,-1), up (-1,0),
+ * up-right (-1,+1), up-left (-1,-1).  The sum is taken in a fixed order:
+ *   paths = 4:  S = ((L_right + L_left) + L_down) + L_up
+ *   paths = 8:  S = ((((((L_right + L_left) + L_down) + L_down_right) + L_down_left) + L_up) + L_up_right) + L_up_left
+ * Outputs: S (optional), idx [frames][H][W] = argmin_d S (int64, the first index wins), best = S[idx] (f32).  S and best
+ * are in COST sign also when maximise != 0 (lower is better; they are sums of -vol plus penalties).
+ * Arguments: 0 <= P1 <= P2, both finite.  Inputs must be finite; non-finite inputs give unspecified values.
+ *
+ * ctd_sgm_aggregate_f32: S_out [frames][D][H][W] or NULL; when NULL, S lives in the workspace
+ *   (ctd_sgm_workspace_bytes(..., want_volume = 0) = frames * D * H * W floats, 16-byte aligned; 0 bytes and no workspace
+ *   with want_volume != 0).  vol is never written and must not overlap S_out or the workspace; the contents of S_out and
+ *   of the workspace on entry do not matter.  Every D in [1, 256] and every H, W >= 1 is supported.
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for paths outside {4, 8}, p1 < 0, p2 < p1, a non-finite penalty, a
+ *   size <= 0, frames * D * H * W >= 2^31 or a NULL vol / idx / best; CTD_ERR_UNSUPPORTED for D > 256;
+ *   CTD_ERR_WORKSPACE for a NULL, short or misaligned workspace when S_out is NULL.  The workspace query returns 0 for
+ *   the first two.
+ * -------------------------------------------------------------------------------------- */
+size_t ctd_sgm_workspace_bytes(int frames, int D, int H, int W, int paths, int want_volume);
+int ctd_sgm_aggregate_f32(const float* vol, int maximise, float p1, float p2, int paths, float* S_out, int64_t* idx,
+                          float* best, int frames, int D, int H, int W, void* workspace, size_t workspace_bytes,
+                          int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
  * model/networks.py:507-533 (ReflectionPad2d + two all-ones Conv2d + 6 elementwise ops).
  *   x [N][1][H][W] -> y = (x-avg)/std, std  (both [N][1][H][W]);  radius < min(H, W)
