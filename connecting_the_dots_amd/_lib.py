@@ -85,6 +85,11 @@ SIGNATURES = {
     "ctd_sgm_workspace_bytes": (_c_size_t, [_c_int] * 6),
     "ctd_sgm_aggregate_f32": (_c_int, [_vp, _c_int, _c_float, _c_float, _c_int, _vp, _vp, _vp] + [_c_int] * 4 +
                               [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_disp_components_workspace_bytes": (_c_size_t, [_c_int] * 3),
+    "ctd_disp_components_f32": (_c_int, [_vp, _vp, _c_float, _c_int, _vp, _vp] + [_c_int] * 3 + [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_disp_speckle_f32": (_c_int, [_vp, _vp, _c_float, _c_int, _c_int, _vp, _vp] + [_c_int] * 3 +
+                             [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_disp_median_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp] + [_c_int] * 4 + [_vp]),
     "ctd_lcn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_fast_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_datagen_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),

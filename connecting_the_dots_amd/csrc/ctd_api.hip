@@ -619,6 +619,64 @@ int ctd_sgm_aggregate_f32(const float* vol, int maximise, float p1, float p2, in
                            (hipStream_t)stream);
 }
 
+// ---- disparity post-filters (disp_filter.hip) ----
+static bool disp_filter_args_ok(int frames, int H, int W) {
+  return frames >= 0 && H > 0 && W > 0 && (double)H * W < 2147483648.0 && (double)frames * H * W < 2147483648.0;
+}
+
+static bool disp_link_args_ok(float max_diff, int connectivity) {
+  return max_diff >= 0.f && (connectivity == 4 || connectivity == 8);                           // (a NaN fails >=)
+}
+
+size_t ctd_disp_components_workspace_bytes(int frames, int H, int W) {
+  if (frames <= 0 || !disp_filter_args_ok(frames, H, W)) return 0;
+  return sizeof(int) * disp_components_workspace_ints(frames, H, W);
+}
+
+static int disp_components_call(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int max_size,
+                                int32_t* label, int32_t* size, uint8_t* keep, int frames, int H, int W, void* workspace,
+                                size_t workspace_bytes, int device, void* stream) {
+  if (frames == 0) return CTD_OK;
+  if (!disp_filter_supported(frames, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < ctd_disp_components_workspace_bytes(frames, H, W) || ((uintptr_t)workspace & 15))
+    return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_components_f32(disp, valid, max_diff, connectivity, max_size, label, size, keep, frames, H, W,
+                             (int*)workspace, (hipStream_t)stream);
+}
+
+int ctd_disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int32_t* label,
+                            int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes, int device,
+                            void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || !disp_link_args_ok(max_diff, connectivity)) return CTD_ERR_INVALID_ARG;
+  if (!disp || !label || !size) return CTD_ERR_INVALID_ARG;
+  return disp_components_call(disp, valid, max_diff, connectivity, 0, label, size, nullptr, frames, H, W, workspace,
+                              workspace_bytes, device, stream);
+}
+
+int ctd_disp_speckle_f32(const float* disp, const uint8_t* valid, float max_diff, int max_size, int connectivity,
+                         uint8_t* keep, int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes,
+                         int device, void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || !disp_link_args_ok(max_diff, connectivity) || max_size < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (!disp || !keep) return CTD_ERR_INVALID_ARG;
+  return disp_components_call(disp, valid, max_diff, connectivity, max_size, nullptr, size, keep, frames, H, W, workspace,
+                              workspace_bytes, device, stream);
+}
+
+int ctd_disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
+                        int frames, int H, int W, int device, void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || (window != 3 && window != 5 && window != 7) || fill_min < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (!disp || !out || !valid_out || out == disp || (const uint8_t*)valid_out == valid) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!disp_filter_supported(frames, H, W)) return CTD_ERR_UNSUPPORTED;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_median_f32(disp, valid, window, fill_min, out, valid_out, frames, H, W, (hipStream_t)stream);
+}
+
 int ctd_disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float baseline_focal, int device, void* stream) {
   if (n < 0) return CTD_ERR_INVALID_ARG;
   if (n == 0) return CTD_OK;

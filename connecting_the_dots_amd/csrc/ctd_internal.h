@@ -152,6 +152,15 @@ bool sgm_supported(int frames, int D, int H, int W);
 int sgm_aggregate_f32(const float* vol, bool maximise, float p1, float p2, int paths, float* S, int64_t* idx, float* best,
                       int frames, int D, int H, int W, hipStream_t stream);
 
+// disp_filter.hip
+bool disp_filter_supported(int frames, int H, int W);
+size_t disp_components_workspace_ints(int frames, int H, int W);
+int disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int max_size,
+                        int32_t* label, int32_t* size, uint8_t* keep, int frames, int H, int W, int* workspace,
+                        hipStream_t stream);
+int disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
+                    int frames, int H, int W, hipStream_t stream);
+
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

@@ -356,6 +356,55 @@ int ctd_sgm_aggregate_f32(const float* vol, int maximise, float p1, float p2, in
                           int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
+ * Disparity post-filters (additive in ABI version 5): the step after the validity flags, on the disparity map itself --
+ * speckle removal (connected components) and a validity-aware median.  Both look at a pixel's neighbours.
+ *
+ * Common terms.  All maps are [frames][H][W]; disparities are f32.  A pixel is LIVE when its `valid` byte is nonzero and
+ * its disparity is finite; a NULL `valid` counts as nonzero everywhere.  The inputs are never written and the outputs
+ * must not overlap them or the workspace.
+ *
+ * 1. Components, ctd_disp_components_f32.  Two neighbouring pixels p, q are LINKED when both are live and
+ *      fabsf(disp[p] - disp[q]) <= max_diff                                              (one f32 subtraction).
+ *    Neighbours are the 4 edge neighbours (connectivity = 4) plus the 4 diagonal ones (connectivity = 8), inside the
+ *    frame; nothing crosses frames.  Components are the transitive closure of the links (a chain 0, 1, 2, 3 with
+ *    max_diff = 1 is one component although its ends differ by 3).  Outputs:
+ *      label (int32) = the smallest in-frame linear index h * W + w among the pixels of p's component; -1 if p is not live
+ *      size  (int32) = the number of pixels of p's component; 0 if p is not live
+ *    Both are fully determined: the kernels use integer atomics only (a minimum for the unions, an add for the counts),
+ *    and the root of a set is its smallest index whatever order they land in.  max_diff = +inf is allowed and gives the
+ *    components of the live mask.  Every H, W >= 1 is supported.
+ *    Workspace: ctd_disp_components_workspace_bytes(frames, H, W) bytes, 16-byte aligned (three int32 per pixel); its
+ *    contents on entry, and those of the outputs, do not matter.
+ * 2. Speckle filter, ctd_disp_speckle_f32.  With the components of 1:
+ *      keep (uint8) = 1 where p is live and size > max_size, 0 elsewhere
+ *    i.e. components of at most max_size pixels are removed (the rule of OpenCV's filterSpeckles); max_size = 0 keeps
+ *    every live pixel.  `size` is optional (NULL: not written).  Same workspace as 1.
+ * 3. Masked median, ctd_disp_median_f32, window = 3, 5 or 7.  For pixel p collect the disparities of the live pixels
+ *    inside the window x window square centred on p -- in-image pixels only, no border replication -- and let m be their
+ *    number.  Put them in ascending order; equal values (the two signed zeros compare equal) keep the raster order of
+ *    the window, rows first.
+ *      p live:                                   out = the element of rank (m - 1) / 2 (integer division: the lower
+ *                                                median; p itself is in the window, so m >= 1), valid_out = 1
+ *      p not live, fill_min > 0, m >= fill_min:  the same (hole filling)
+ *      otherwise:                                out = NaN, valid_out = 0
+ *    The result is a selection, so it is defined bit for bit.  No workspace.
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for a negative or NaN max_diff, a connectivity outside {4, 8}, a
+ *   negative max_size or fill_min, a window outside {3, 5, 7}, H <= 0, W <= 0, frames < 0, H * W >= 2^31,
+ *   frames * H * W >= 2^31, a NULL disp or output other than the speckle filter's `size`, or a median output that is
+ *   one of its inputs; CTD_ERR_WORKSPACE for a NULL, short or misaligned workspace.  frames == 0 is CTD_OK and touches
+ *   nothing.  The workspace query returns 0 for sizes the calls reject.
+ * -------------------------------------------------------------------------------------- */
+size_t ctd_disp_components_workspace_bytes(int frames, int H, int W);
+int ctd_disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int32_t* label,
+                            int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes, int device,
+                            void* stream);
+int ctd_disp_speckle_f32(const float* disp, const uint8_t* valid, float max_diff, int max_size, int connectivity,
+                         uint8_t* keep, int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes,
+                         int device, void* stream);
+int ctd_disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
+                        int frames, int H, int W, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
  * model/networks.py:507-533 (ReflectionPad2d + two all-ones Conv2d + 6 elementwise ops).
  *   x [N][1][H][W] -> y = (x-avg)/std, std  (both [N][1][H][W]);  radius < min(H, W)
