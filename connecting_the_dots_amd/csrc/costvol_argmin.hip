@@ -1,7 +1,7 @@
 // costvol_argmin.hip -- argmin over the disparities of the SAD / soft-census cost volume without the volume
 // (ctd_costvol_argmin_f32), with the indices of the reference-order volume (ctd_costvol_f32) bit for bit.
 //
-//   1. ranking pass: the tolerance-level volume kernel in its ranking instantiation (photometric_fast.hip) writes one
+//   1. ranking pass: the tolerance-level volume kernel in its ranking instantiation (costvol_fast.hip) writes one
 //      Top2 triple (b1, i1, b2) per (pixel, 128 disparities) into the workspace instead of the costs;
 //   2. combine pass: one thread per pixel merges its chunk triples into idx / best and puts the pixel on the work list
 //      unless the fast bound proves the fast winner is the exact one (margin below);

@@ -94,6 +94,7 @@ int photometric_fwd_fast_f32(const float* es, const float* ta, float* out, int B
 int photometric_bwd_fast_f32(const float* es, const float* ta, const float* go, float* gi, int B, int C, int H, int W,
                              int bs, int type, float eps, hipStream_t s);
 
+// pattern_loss.hip
 size_t pattern_loss_workspace_bytes(int B, int H, int W);
 int pattern_loss_fwd_f32(const float* disp, const float* im, const float* mask, const float* pattern, float* proj,
                          float* terms, int B, int H, int W, int type, float eps, void* ws, size_t ws_bytes,
@@ -108,6 +109,7 @@ int pattern_loss_multi_fwd_f32(int n_levels, const ctd_pattern_level* levels, fl
 int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, const float* terms, const float* grad_vals,
                                int type, float eps, hipStream_t stream);
 
+// costvol_fast.hip
 int costvol_fast_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W,
                      int D, int bs, int type, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream);
 // ranking instantiations of the volume kernels (Top2Planes: ctd_top2.h) and the argmin built on them

@@ -1,5 +1,5 @@
 // ctd_ncc_point.h -- one NCC output in the reference's operation order from windows staged in LDS.
-// XCorrVolFunctor<T>::operator()  /root/reference/torchext/ext/ext.h:120-191 (two passes over the window,
+// XCorrVolFunctor<T>::operator()  torchext/ext/ext.h:120-191 (two passes over the window,
 // means first, channels accumulated in order).  Used by the exact re-scoring of the ranked argmax
 // (argmax_rerank.hip); bit-identical to the reference's FMA-free CPU build.
 #ifndef CTD_NCC_POINT_H

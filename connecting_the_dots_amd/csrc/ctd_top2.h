@@ -1,5 +1,5 @@
 // ctd_top2.h -- best / runner-up of a set of block costs, the reduction of the volume-free cost argmin
-// (ctd_costvol_argmin_f32): the ranking instantiations of the cost-volume kernels (photometric_fast.hip) and the
+// (ctd_costvol_argmin_f32): the ranking instantiations of the cost-volume kernels (costvol_fast.hip) and the
 // combine pass (costvol_argmin.hip).
 //
 // Top2 {b1, i1, b2} of a set S of (cost, d): b1 = min cost, i1 = the LOWEST d with that cost, b2 = min cost over S

@@ -1,6 +1,6 @@
 // nn_ops.hip -- nearest-neighbour consistency ops of the torchext surface.
 //
-//   nn          NNFunctor<T,3>      /root/reference/torchext/ext/ext.h:13-47
+//   nn          NNFunctor<T,3>      torchext/ext/ext.h:13-47
 //   crosscheck  CrossCheckFunctor   ext.h:49-66
 //   proj_nn     ProjNNFunctor<T,3>  ext.h:68-117
 //

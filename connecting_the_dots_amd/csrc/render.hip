@@ -1,6 +1,6 @@
 // render.hip -- synthetic structured-light rendering: the reference's brute-force ray caster
 // with projector inpainting, RenderProjectorFunctor<float>::operator()
-// (/root/reference/renderer/render/render.h:251-364; ray/mesh intersection geometry.h:201-258, camera
+// (renderer/render/render.h:251-364; ray/mesh intersection geometry.h:201-258, camera
 // render.h:12-87, Phong shader geometry.h:262-292, bilinear pattern fetch render.h:228-249; launched by
 // render_gpu.cu through iterate_cuda, one thread per camera pixel).
 //

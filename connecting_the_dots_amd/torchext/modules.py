@@ -69,7 +69,7 @@ class RectifiedPatternSimilarityLoss(torch.nn.Module):
         self.pattern, self.u0, self.v0 = self.pattern.to(dev), self.u0.to(dev), self.v0.to(dev)
         B = disp0.shape[0]
         if self._fused(disp0, im, std):
-            # algo='fast': warp + block loss + masked sums in one kernel each way (photometric_fast.hip)
+            # algo='fast': warp + block loss + masked sums in one kernel each way (pattern_loss.hip)
             _, pattern_proj, terms = pattern_loss(disp0.contiguous(), im.contiguous(),  # noqa: F405
                                                   None if std is None else std.contiguous(), self.pattern,
                                                   self.loss_type, self.loss_eps)

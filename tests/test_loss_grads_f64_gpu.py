@@ -1,6 +1,6 @@
 """Training-loss kernels, values and every gradient, elementwise against float64 stock-torch references
 (tests/f64_refs.py) at the shapes the 64 x 4 tiles of losses.hip and the 64 x 8 tiles (9-wide halo) of
-photometric_fast.hip meet in training, including their ragged edges.
+photometric_fast.hip and pattern_loss.hip meet in training, including their ragged edges.
 
 Tolerance rule (the same for every case; nothing is tuned per case):
   * every element outside the mask: |hip - f64| <= r |f64| + a max|f64| + p, with r = 1e-5, a = 2e-5;

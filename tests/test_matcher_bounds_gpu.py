@@ -9,7 +9,7 @@ ones must meet the bound (and the error model against float64 truth), guard outp
 decided by the pre-pass's own rounding) one or the other.  The ranked argmax paths must give the exact kernel's indices
 on the same frames.
 
-Cost volumes (photometric_fast.hip, costvol_argmin.hip): the premise of costvol_argmin's proof, |f(d) - x(d)| <= 1e-5
+Cost volumes (costvol_fast.hip, costvol_argmin.hip): the premise of costvol_argmin's proof, |f(d) - x(d)| <= 1e-5
 x(d) + 1e-6 for every d, elementwise; indices equal to the exact volume's first-index argmin; and the census-SAD
 gradient's sign at census differences next to zero.
 

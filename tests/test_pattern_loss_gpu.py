@@ -98,26 +98,60 @@ def test_fused_terms_support_cross_rank_ratio():
     assert torch.allclose(d1.grad, d2.grad, rtol=1e-5, atol=1e-9)
 
 
-def test_multi_level_launch_equals_per_level_calls():
+TYPES = ["mse", "sad", "census_mse", "census_sad"]
+
+
+@pytest.mark.parametrize("ty", TYPES)
+def test_multi_level_launch_equals_per_level_calls(ty):
     """N2: four pyramid levels (480x640 ... 60x80, as exp_synph.py trains on) in one launch each way give the
-    very same numbers as four single-level calls (same tile code, same fixed-order reductions)"""
+    very same numbers as four single-level calls (same tile code, same fixed-order reductions).  The types other than
+    the training one run two small levels (37x70, 19x35: ragged tiles both ways) -- what differs between the types is
+    the instantiation a call reaches, not the level walk."""
     from connecting_the_dots_amd import torchext as te
     torch.manual_seed(8)
     B = 2
+    sizes = [(480 >> s, 640 >> s) for s in range(4)] if ty == "census_sad" else [(37, 70), (19, 35)]
+    n = len(sizes)
     disps, ims, stds, pats = [], [], [], []
-    for s in range(4):
-        H, W = 480 >> s, 640 >> s
+    for s, (H, W) in enumerate(sizes):
         pats.append(torch.randn(1, 1, H, W, device="cuda"))
         ims.append(torch.randn(B, 1, H, W, device="cuda"))
-        stds.append(None if s == 3 else 0.05 + torch.rand(B, 1, H, W, device="cuda"))
+        stds.append(None if s == n - 1 else 0.05 + torch.rand(B, 1, H, W, device="cuda"))
         disps.append(torch.rand(B, 1, H, W, device="cuda") * (60 >> s))
     da = [d.clone().requires_grad_(True) for d in disps]
-    vals, terms, projs = te.pattern_loss_multi(da, ims, stds, pats, "census_sad", 0.5)
-    w = torch.tensor([1.0, 0.5, 0.25, 2.0], device="cuda")
+    vals, terms, projs = te.pattern_loss_multi(da, ims, stds, pats, ty, 0.5)
+    w = torch.tensor([1.0, 0.5, 0.25, 2.0], device="cuda")[:n]
     (vals * w).sum().backward()
-    for s in range(4):
+    for s in range(n):
         d = disps[s].clone().requires_grad_(True)
-        v, p, t = te.pattern_loss(d, ims[s], stds[s], pats[s], "census_sad", 0.5)
+        v, p, t = te.pattern_loss(d, ims[s], stds[s], pats[s], ty, 0.5)
         (v * w[s]).backward()
         assert torch.equal(v, vals[s]) and torch.equal(t, terms[s]) and torch.equal(p, projs[s])
         assert torch.equal(d.grad, da[s].grad)
+
+
+def test_fused_value_is_the_block_loss_of_its_type():
+    """Every loss type of the fused forward against the composition it fuses: the block loss (fast kernels) of the
+    returned warped pattern, then the masked ratio sum(std * diff) / sum(std) in float64 on the host.  2 x 11 x 70: two
+    column tiles (the second ragged) and two row tiles.  Both sides evaluate the same per-pixel block loss on the same
+    samples, so only the order of the sums differs: relative 1e-5, the figure of
+    test_fused_matches_composition_at_training_size for this quantity.  The four values lie more than 1e-3 apart on
+    this input, so a call that reaches another type's kernel cannot pass."""
+    from connecting_the_dots_amd import torchext as te
+    torch.manual_seed(11)
+    B, H, W = 2, 11, 70
+    pat = torch.randn(1, 1, H, W, device="cuda")
+    im = torch.randn(B, 1, H, W, device="cuda")
+    std = 0.05 + torch.rand(B, 1, H, W, device="cuda")
+    d = torch.rand(B, 1, H, W, device="cuda") * 20
+    vals = {}
+    for ty in TYPES:
+        v, proj, _ = te.pattern_loss(d, im, std, pat, ty, 0.5)
+        diff = te.photometric_loss(proj, im, 9, ty, 0.5, algo="fast")
+        want = float((std.double().cpu() * diff.double().cpu()).sum() / std.double().cpu().sum())
+        vals[ty] = float(v)
+        print("pattern_loss %s: fused %.9g composition %.9g rel %.3g" % (ty, vals[ty], want, abs(vals[ty] - want) / abs(want)))
+        assert abs(vals[ty] - want) <= 1e-5 * abs(want), (ty, vals[ty], want)
+    for i, a in enumerate(TYPES):
+        for b in TYPES[i + 1:]:
+            assert abs(vals[a] - vals[b]) > 1e-3 * max(abs(vals[a]), abs(vals[b])), (a, b, vals[a], vals[b])

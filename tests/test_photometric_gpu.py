@@ -201,9 +201,11 @@ def test_fast_full_size_properties(te):
 
 
 @pytest.mark.parametrize("ty", TYPES)
-@pytest.mark.parametrize("shape", [(24, 150, 40, 9), (37, 64, 7, 5), (9, 70, 33, 9), (16, 200, 70, 3)])
+@pytest.mark.parametrize("shape", [(24, 150, 40, 9), (37, 64, 7, 5), (9, 70, 33, 9), (16, 200, 70, 3),
+                                   (11, 70, 130, 7)])
 def test_costvol_fast_vs_oracle(te, oracle, ty, shape):
-    """A6, algo='fast': image borders (both clamps), disparities beyond one LDS chunk (32), D not a multiple of 8"""
+    """A6, algo='fast': image borders (both clamps), disparities beyond one LDS chunk (32), D not a multiple of 8; every
+    block size (block 7: ragged second tiles both ways, D past the 128-disparity chunk of the census kernel)"""
     H, W, D, bs = shape
     rs = np.random.RandomState(sum(shape))
     im = rs.randn(H, W).astype(np.float32)

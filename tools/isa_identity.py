@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Is the device code of the fast NCC family the same code as at another commit?  (No GPU needed.)
+"""Is the library's device code the same code as at another commit?  (No GPU needed.)
 
     python tools/isa_identity.py --base REV          # REV: a git revision, e.g. HEAD~1
     python tools/isa_identity.py --base-dir TREE     # or a checked-out tree of that revision
+    python tools/isa_identity.py --base REV --only photometric_fast pattern_loss costvol_fast    # these files alone
 
-Compiles every csrc file of the family, as it is at the base and as it is in the working tree, to gfx950 assembly with
+Compiles every csrc/*.hip present in either tree (--only NAME ...: the files of those base names, where they exist), as
+it is at the base and as it is in the working tree, to gfx950 assembly with
 the flags of connecting_the_dots_amd/build.py plus `--cuda-device-only -S` (into a temporary directory, never into the
 tree) and compares per kernel symbol, whichever file defines it:
   * the set of .amdhsa_kernel symbols (each exactly once on either side);
@@ -16,6 +18,7 @@ after `--` (e.g. `-- -DCTD_STAMPS` compares the diagnostic build).
 """
 import argparse
 import difflib
+import glob
 import os
 import re
 import subprocess
@@ -25,15 +28,17 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "connecting_the_dots_amd/csrc"
-# every translation unit that holds, or has held, a kernel of the family
-FAMILY = ["ncc_fast", "ncc_prepass", "ncc_fixup", "ncc_tiles", "ncc_t256", "ncc_alld", "costvol_sep"]
 
 sys.path.insert(0, ROOT)
 from connecting_the_dots_amd.build import FLAGS, HIPCC  # noqa: E402
 
 
-def compile_family(tree, out_dir, extra):
-    srcs = [os.path.join(tree, CSRC, n + ".hip") for n in FAMILY]
+def names_in(tree):
+    return {os.path.basename(s)[:-4] for s in glob.glob(os.path.join(tree, CSRC, "*.hip"))}
+
+
+def compile_family(tree, family, out_dir, extra):
+    srcs = [os.path.join(tree, CSRC, n + ".hip") for n in family]
     srcs = [s for s in srcs if os.path.exists(s)]
     os.makedirs(out_dir, exist_ok=True)
 
@@ -89,6 +94,7 @@ def main():
     g.add_argument("--base", help="git revision to compare the working tree with")
     g.add_argument("--base-dir", help="checked-out tree of the base revision")
     ap.add_argument("--show", type=int, default=12, help="diff lines to print per differing kernel")
+    ap.add_argument("--only", nargs="+", metavar="NAME", help="compare these csrc files only (base names, no .hip)")
     ap.add_argument("extra", nargs="*", help="extra compiler flags (after --)")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="isa_identity_") as tmp:
@@ -99,8 +105,14 @@ def main():
             tar = subprocess.Popen(["git", "-C", ROOT, "archive", args.base, CSRC, "include"], stdout=subprocess.PIPE)
             subprocess.check_call(["tar", "-x", "-C", base_tree], stdin=tar.stdout)
             assert tar.wait() == 0
-        old, dup_old = collect(compile_family(base_tree, os.path.join(tmp, "base"), args.extra))
-        new, dup_new = collect(compile_family(ROOT, os.path.join(tmp, "new"), args.extra))
+        family = sorted(names_in(base_tree) | names_in(ROOT))       # a kernel may have moved to a file the base lacks
+        if args.only:
+            unknown = set(args.only) - set(family)
+            if unknown:
+                ap.error("no such csrc file in either tree: " + ", ".join(sorted(unknown)))
+            family = sorted(args.only)
+        old, dup_old = collect(compile_family(base_tree, family, os.path.join(tmp, "base"), args.extra))
+        new, dup_new = collect(compile_family(ROOT, family, os.path.join(tmp, "new"), args.extra))
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
