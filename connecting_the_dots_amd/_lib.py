@@ -90,6 +90,10 @@ SIGNATURES = {
     "ctd_disp_speckle_f32": (_c_int, [_vp, _vp, _c_float, _c_int, _c_int, _vp, _vp] + [_c_int] * 3 +
                              [_vp, _c_size_t, _c_int, _vp]),
     "ctd_disp_median_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp] + [_c_int] * 4 + [_vp]),
+    "ctd_depth_consistency_f32": (_c_int, [_vp] * 6 + [_c_float, _c_float, _c_int] + [_vp] * 3 + [_c_int] * 4 + [_c_int, _vp]),
+    "ctd_depth_fuse_workspace_bytes": (_c_size_t, [_c_int] * 4),
+    "ctd_depth_fuse_points_f32": (_c_int, [_vp] * 6 + [_c_float, _c_float, _c_int, _c_int] + [_vp] * 6 + [_c_int] * 4 +
+                                  [_vp, _c_size_t, _c_int, _vp]),
     "ctd_lcn_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_fast_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),
     "ctd_lcn_datagen_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_c_float, _c_int, _vp]),

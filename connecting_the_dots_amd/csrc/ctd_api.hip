@@ -677,6 +677,76 @@ int ctd_disp_median_f32(const float* disp, const uint8_t* valid, int window, int
   return disp_median_f32(disp, valid, window, fill_min, out, valid_out, frames, H, W, (hipStream_t)stream);
 }
 
+// ---- multi-view depth consistency and point fusion (depth_fusion.hip) ----
+static bool depth_fusion_sizes_ok(int B, int V, int H, int W) {
+  // H, W <= 2^24: the bounds of the projected pixel are compared in f32, where W - 1 and H - 1 must be exact
+  return B >= 0 && V >= 1 && H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24) &&
+         (double)B * V * H * W < 2147483648.0;
+}
+
+static bool depth_fusion_params_ok(float max_px, float max_rel, int min_views) {
+  const float big = 3.402823466e38f;                                                          // (a NaN fails >=)
+  return max_px >= 0.f && max_px <= big && max_rel >= 0.f && max_rel <= big && min_views >= 0 && min_views <= 255;
+}
+
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+// true when one of the first n_out spans (the buffers a call writes) shares a byte with any other span; NULL spans are absent
+static bool spans_overlap(const Span* s, int n_out, int n) {
+  for (int i = 0; i < n_out; ++i)
+    for (int j = 0; j < n; ++j) {
+      if (j == i || (j < n_out && j < i) || !s[i].p || !s[j].p || !s[i].bytes || !s[j].bytes) continue;
+      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) return true;
+    }
+  return false;
+}
+
+int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
+                              float* fused, int B, int V, int H, int W, int device, void* stream) {
+  if (!depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_params_ok(max_px, max_rel, min_views)) return CTD_ERR_INVALID_ARG;
+  if (!depth || !ray || !K || !R || !t || !count || !keep || !fused) return CTD_ERR_INVALID_ARG;
+  if (V > 64 || !depth_fusion_supported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  const size_t n = (size_t)B * V * H * W, views = (size_t)B * V;
+  const Span s[] = {{count, n}, {keep, n}, {fused, 4 * n}, {depth, 4 * n}, {valid, n}, {ray, 12 * (size_t)H * W},
+                    {K, 36}, {R, 36 * views}, {t, 12 * views}};
+  if (spans_overlap(s, 3, 9)) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return depth_consistency_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, count, keep, fused, B, V, H, W,
+                               (hipStream_t)stream);
+}
+
+size_t ctd_depth_fuse_workspace_bytes(int B, int V, int H, int W) {
+  if (B <= 0 || V > 64 || !depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_supported(B, V, H, W)) return 0;
+  return depth_fuse_workspace_bytes(B, V, H, W);
+}
+
+int ctd_depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
+                              int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B,
+                              int V, int H, int W, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_params_ok(max_px, max_rel, min_views)) return CTD_ERR_INVALID_ARG;
+  if (!depth || !ray || !K || !R || !t || !points || !src || !n_per_track) return CTD_ERR_INVALID_ARG;
+  if (V > 64 || !depth_fusion_supported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  const size_t n = (size_t)B * V * H * W, views = (size_t)B * V;
+  const size_t need = ctd_depth_fuse_workspace_bytes(B, V, H, W);
+  const Span s[] = {{points, 12 * n}, {src, 8 * n}, {n_per_track, 8 * (size_t)B}, {count, n}, {keep, n}, {fused, 4 * n},
+                    {workspace, need}, {depth, 4 * n}, {valid, n}, {ray, 12 * (size_t)H * W}, {K, 36}, {R, 36 * views},
+                    {t, 12 * views}};
+  if (spans_overlap(s, 7, 13)) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return depth_fuse_points_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, dedupe, points, src, n_per_track,
+                               count, keep, fused, B, V, H, W, workspace, (hipStream_t)stream);
+}
+
 int ctd_disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float baseline_focal, int device, void* stream) {
   if (n < 0) return CTD_ERR_INVALID_ARG;
   if (n == 0) return CTD_OK;

@@ -163,6 +163,17 @@ int disp_components_f32(const float* disp, const uint8_t* valid, float max_diff,
 int disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
                     int frames, int H, int W, hipStream_t stream);
 
+// depth_fusion.hip
+bool depth_fusion_supported(int B, int V, int H, int W);
+size_t depth_fuse_workspace_bytes(int B, int V, int H, int W);
+int depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                          const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
+                          float* fused, int B, int V, int H, int W, hipStream_t stream);
+int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                          const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
+                          int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B, int V,
+                          int H, int W, void* workspace, hipStream_t stream);
+
 // lcn.hip
 int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);
 int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream);

@@ -1,0 +1,278 @@
+// depth_fusion.hip -- multi-view depth consistency and point-cloud fusion of a track's depth maps [B][V][H][W]
+// (ctd_depth_consistency_f32, ctd_depth_fuse_points_f32; the rules are stated word for word in include/ctd_hip.h).
+//
+// view_match() is the one place that projects a pixel of view r into view s, samples the nearest source pixel, projects
+// it back and decides consistency; the consistency pass and the emit pass of the fusion both call it, so the two cannot
+// drift apart.  Every product and sum is in the association of the header (that of geo_forward in losses.hip); the build
+// never contracts them.  Poses and K are indexed by block-uniform values only (track, view, loop counter): scalar loads.
+//   depth_consistency_kernel -- a 64 x 4 tile of one view, thread = reference pixel, loop over the source views.
+//     Per pixel: 5 B read + 12 B ray, per source view one 5 B gather + 12 B ray of the pixel hit; 6 B written.
+//   fuse_count_kernel   -- 256 consecutive pixels of ONE view (a chunk never crosses a view, so the pose stays uniform
+//     and the workgroups are in ascending `src` order): the emit flag (with dedupe: the projections into the views
+//     s < r again, and keep of the pixel hit) and, from one ballot per wavefront, the workgroup's number of flags.
+//     Per pixel: 1 B read + 1 B written; with dedupe, for a kept pixel, 4 + 12 B and per earlier view 5 + 12 + 1 B.
+//   fuse_scan_kernel    -- ONE workgroup: exclusive scan of the workgroup counts, 1024 at a time with a carry, then the
+//     per-track totals as differences of the scanned offsets.
+//   fuse_scatter_kernel -- the chunks again: offset of the workgroup + flags before the lane (ballot), and for a flagged
+//     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
+// Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
+#include "ctd_internal.h"
+
+namespace ctd {
+namespace {
+
+constexpr int kChunk = 256;                                   // pixels per workgroup of the count and scatter kernels
+constexpr int kScan = 1024;                                   // threads of the scan workgroup
+
+struct FuseTol {
+  float max_px2, max_rel;                                     // max_px * max_px (one f32 product), max_rel
+};
+
+__device__ inline bool live_at(const float* __restrict__ depth, const uint8_t* __restrict__ valid, long g) {
+  const float d = depth[g];
+  return (!valid || valid[g]) && d > 0.f && d < __builtin_inff();
+}
+
+// depth d along ray3 in view a -> uvd in view b (X_cam = R X_world + t)
+__device__ inline void view_transform(const float* __restrict__ ray3, float d, const float* __restrict__ Ra,
+                                      const float* __restrict__ ta, const float* __restrict__ Rb,
+                                      const float* __restrict__ tb, const float* __restrict__ K, float* uvd) {
+  float p[3], q[3], s[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) p[i] = d * ray3[i] - ta[i];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) q[j] = p[0] * Ra[0 * 3 + j] + p[1] * Ra[1 * 3 + j] + p[2] * Ra[2 * 3 + j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) s[j] = q[0] * Rb[j * 3 + 0] + q[1] * Rb[j * 3 + 1] + q[2] * Rb[j * 3 + 2] + tb[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) uvd[j] = s[0] * K[j * 3 + 0] + s[1] * K[j * 3 + 1] + s[2] * K[j * 3 + 2];
+}
+
+// Steps a, b, c of the header for the live pixel (x, y) of view r, depth d_r, against view s of the same track
+// (depth, valid, R, t point at the track).  true = consistent; q = the source pixel of step a, z = z' of step b.
+__device__ inline bool view_match(const float* __restrict__ depth, const uint8_t* __restrict__ valid,
+                                  const float* __restrict__ ray, const float* __restrict__ K,
+                                  const float* __restrict__ R, const float* __restrict__ t, int r, int s, int H, int W,
+                                  int x, int y, float d_r, FuseTol tol, long& q, float& z) {
+  const long plane = (long)H * W;
+  float uvd[3];
+  view_transform(ray + ((long)y * W + x) * 3, d_r, R + r * 9, t + r * 3, R + s * 9, t + s * 3, K, uvd);
+  if (!(uvd[2] > 0.f)) return false;
+  const float xs = floorf(uvd[0] / uvd[2] + 0.5f), ys = floorf(uvd[1] / uvd[2] + 0.5f);
+  // float compares first (a NaN fails them); W - 1 and H - 1 are exact in f32 (H, W <= 2^24)
+  if (!(xs >= 0.f && xs <= (float)(W - 1) && ys >= 0.f && ys <= (float)(H - 1))) return false;
+  q = (long)(int)ys * W + (int)xs;
+  const long gs = s * plane + q;
+  if (!live_at(depth, valid, gs)) return false;
+  view_transform(ray + q * 3, depth[gs], R + s * 9, t + s * 3, R + r * 9, t + r * 3, K, uvd);
+  if (!(uvd[2] > 0.f)) return false;
+  z = uvd[2];
+  const float du = uvd[0] / uvd[2] - (float)x, dv = uvd[1] / uvd[2] - (float)y;
+  return du * du + dv * dv <= tol.max_px2 && fabsf(z - d_r) <= tol.max_rel * d_r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void depth_consistency_kernel(
+    const float* __restrict__ depth, const uint8_t* __restrict__ valid, const float* __restrict__ ray,
+    const float* __restrict__ K, const float* __restrict__ R, const float* __restrict__ t, uint8_t* __restrict__ count,
+    uint8_t* __restrict__ keep, float* __restrict__ fused, int V, int H, int W, int tiles_x, int tiles, FuseTol tol,
+    int min_views) {
+  const int tile = blockIdx.x % tiles, bv = blockIdx.x / tiles, b = bv / V, r = bv % V;
+  const int x = (tile % tiles_x) * 64 + (threadIdx.x & 63), y = (tile / tiles_x) * 4 + (threadIdx.x >> 6);
+  if (x >= W || y >= H) return;
+  const long plane = (long)H * W, track = (long)b * V * plane, g = (long)bv * plane + (long)y * W + x;
+  depth += track;
+  if (valid) valid += track;
+  R += (long)b * V * 9;
+  t += (long)b * V * 3;
+  const long gl = g - track;
+  const bool live = live_at(depth, valid, gl);
+  const float d_r = depth[gl];
+  int n = 0;
+  float acc = d_r;
+  for (int s = 0; s < V; ++s) {
+    long q;
+    float z;
+    if (live && s != r && view_match(depth, valid, ray, K, R, t, r, s, H, W, x, y, d_r, tol, q, z)) {
+      ++n;
+      acc = acc + z;
+    }
+  }
+  const bool k = live && n >= min_views;
+  if (count) count[g] = (uint8_t)n;
+  keep[g] = k ? 1 : 0;
+  fused[g] = k ? acc / (float)(1 + n) : __builtin_nanf("");
+}
+
+// the chunk of a workgroup: pixel p of view r of track b (p >= plane: past the end of the view)
+struct Chunk {
+  int b, r;
+  long p, g;
+};
+__device__ inline Chunk chunk_of_block(int V, long plane, int chunks) {
+  Chunk c;
+  const int bv = blockIdx.x / chunks;
+  c.b = bv / V;
+  c.r = bv % V;
+  c.p = (long)(blockIdx.x % chunks) * kChunk + threadIdx.x;
+  c.g = (long)bv * plane + c.p;
+  return c;
+}
+
+__global__ __launch_bounds__(kChunk) void fuse_count_kernel(
+    const float* __restrict__ depth, const uint8_t* __restrict__ valid, const float* __restrict__ ray,
+    const float* __restrict__ K, const float* __restrict__ R, const float* __restrict__ t,
+    const uint8_t* __restrict__ keep, uint8_t* __restrict__ emit, int* __restrict__ wg_count, int V, int H, int W,
+    int chunks, FuseTol tol, int dedupe) {
+  __shared__ int wave_n[kChunk / 64];
+  const long plane = (long)H * W;
+  const Chunk c = chunk_of_block(V, plane, chunks);
+  bool e = false;
+  if (c.p < plane) {
+    e = keep[c.g] != 0;
+    if (e && dedupe && c.r > 0) {                             // first view wins: an earlier view that confirms and keeps it
+      const long track = (long)c.b * V * plane;
+      const float* dt = depth + track;
+      const uint8_t* vt = valid ? valid + track : nullptr;
+      const float d_r = dt[c.g - track];
+      const int x = (int)(c.p % W), y = (int)(c.p / W);
+      for (int s = 0; s < c.r; ++s) {
+        long q;
+        float z;
+        if (e && view_match(dt, vt, ray, K, R + (long)c.b * V * 9, t + (long)c.b * V * 3, c.r, s, H, W, x, y, d_r, tol,
+                            q, z) &&
+            keep[track + s * plane + q])
+          e = false;
+      }
+    }
+    emit[c.g] = e ? 1 : 0;
+  }
+  const int n = __popcll(__ballot(e));
+  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) wg_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+
+// offsets[i] = counts[0] + ... + counts[i-1] for i = 0 .. n (the scan may run in place); n_per_track from the offsets
+__global__ __launch_bounds__(kScan) void fuse_scan_kernel(int* offsets, int n, int per_track, int64_t* __restrict__ n_per_track,
+                                                          int B) {
+  __shared__ int wave_sum[kScan / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;
+  for (int base = 0; base < n; base += kScan) {
+    const int i = base + tid;
+    const int v = i < n ? offsets[i] : 0;
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kScan / 64; ++w) {
+      before += w < wave ? wave_sum[w] : 0;
+      total += wave_sum[w];
+    }
+    if (i < n) offsets[i] = carry + before + incl - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (tid == 0) offsets[n] = carry;
+  __syncthreads();                                            // the offsets this workgroup wrote are read back below
+  for (int b = tid; b < B; b += kScan)
+    n_per_track[b] = (int64_t)(offsets[(long)(b + 1) * per_track] - offsets[(long)b * per_track]);
+}
+
+__global__ __launch_bounds__(kChunk) void fuse_scatter_kernel(
+    const uint8_t* __restrict__ emit, const float* __restrict__ fused, const float* __restrict__ ray,
+    const float* __restrict__ R, const float* __restrict__ t, const int* __restrict__ offsets, float* __restrict__ points,
+    int64_t* __restrict__ src, int V, int H, int W, int chunks) {
+  __shared__ int wave_n[kChunk / 64];
+  const long plane = (long)H * W;
+  const Chunk c = chunk_of_block(V, plane, chunks);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool e = c.p < plane && emit[c.g] != 0;
+  const unsigned long long bits = __ballot(e);
+  if (lane == 0) wave_n[wave] = __popcll(bits);
+  __syncthreads();
+  if (!e) return;
+  long o = offsets[blockIdx.x] + __popcll(bits & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) o += wave_n[w];
+  const float* Rr = R + ((long)c.b * V + c.r) * 9;
+  const float* tr = t + ((long)c.b * V + c.r) * 3;
+  const float f = fused[c.g];
+  float p[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) p[i] = f * ray[c.p * 3 + i] - tr[i];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) points[o * 3 + j] = p[0] * Rr[0 * 3 + j] + p[1] * Rr[1 * 3 + j] + p[2] * Rr[2 * 3 + j];
+  src[o] = c.g;
+}
+
+inline int chunks_of(int H, int W) { return (int)(((long)H * W + kChunk - 1) / kChunk); }
+
+struct FuseLayout {                                           // byte offsets into the workspace
+  size_t keep, fused, emit, offsets, bytes;
+};
+FuseLayout fuse_layout(int B, int V, int H, int W) {
+  const size_t n = (size_t)B * V * H * W;
+  FuseLayout l;
+  l.keep = 0;
+  l.fused = align_up(n, 256);
+  l.emit = l.fused + align_up(4 * n, 256);
+  l.offsets = l.emit + align_up(n, 256);
+  l.bytes = l.offsets + align_up(sizeof(int) * ((size_t)B * V * chunks_of(H, W) + 1), 256);
+  return l;
+}
+
+}  // namespace
+
+bool depth_fusion_supported(int B, int V, int H, int W) {
+  // a launch stays below 2^32 threads: at most 2^24 - 1 workgroups of 256, for the tiles and for the chunks
+  const double views = (double)B * V;
+  return views * ceil_div(W, 64) * ceil_div(H, 4) < 16777216.0 && views * chunks_of(H, W) < 16777216.0;
+}
+
+size_t depth_fuse_workspace_bytes(int B, int V, int H, int W) { return fuse_layout(B, V, H, W).bytes; }
+
+int depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                          const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
+                          float* fused, int B, int V, int H, int W, hipStream_t stream) {
+  const FuseTol tol = {max_px * max_px, max_rel};
+  const int tiles_x = ceil_div(W, 64), tiles = tiles_x * ceil_div(H, 4);          // <= H * W, so the grid is < 2^31
+  depth_consistency_kernel<<<dim3((unsigned)((long)tiles * B * V)), dim3(256), 0, stream>>>(
+      depth, valid, ray, K, R, t, count, keep, fused, V, H, W, tiles_x, tiles, tol, min_views);
+  CTD_LAUNCH_CHECK();
+  return CTD_OK;
+}
+
+int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                          const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
+                          int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B, int V,
+                          int H, int W, void* workspace, hipStream_t stream) {
+  const FuseLayout l = fuse_layout(B, V, H, W);
+  char* ws = (char*)workspace;
+  if (!keep) keep = (uint8_t*)(ws + l.keep);
+  if (!fused) fused = (float*)(ws + l.fused);
+  uint8_t* emit = (uint8_t*)(ws + l.emit);
+  int* offsets = (int*)(ws + l.offsets);
+  const int st = depth_consistency_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, count, keep, fused, B, V, H,
+                                       W, stream);
+  if (st != CTD_OK) return st;
+  const FuseTol tol = {max_px * max_px, max_rel};
+  const int chunks = chunks_of(H, W), blocks = B * V * chunks;
+  fuse_count_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(depth, valid, ray, K, R, t, keep, emit, offsets,
+                                                                         V, H, W, chunks, tol, dedupe);
+  CTD_LAUNCH_CHECK();
+  fuse_scan_kernel<<<dim3(1), dim3(kScan), 0, stream>>>(offsets, blocks, V * chunks, n_per_track, B);
+  CTD_LAUNCH_CHECK();
+  fuse_scatter_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(emit, fused, ray, R, t, offsets, points, src,
+                                                                           V, H, W, chunks);
+  CTD_LAUNCH_CHECK();
+  return CTD_OK;
+}
+
+}  // namespace ctd

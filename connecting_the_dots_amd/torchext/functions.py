@@ -16,6 +16,7 @@ Additive API (no reference counterpart): `xcorrvol_batch`, `argmax_di
 The default can be changed with the environment variables CTD_NCC_ALGO (xcorrvol family) and CTD_PHOTO_ALGO
 (photometric loss, cost volumes, pattern similarity loss).
 """
+import numbers
 import os
 
 import torch
@@ -1232,6 +1233,99 @@ def disparity_filter(disp, valid=None, max_diff=1.0, max_size=20, connectivity=4
 
 disp_components.__doc__ += _DISP_FILTER_RULE
 disp_speckle.__doc__ += _DISP_FILTER_RULE
+
+
+# --------------------------------------------------------------------------------------
+# Multi-view depth consistency and point-cloud fusion (additive; include/ctd_hip.h states the rules word for word)
+# --------------------------------------------------------------------------------------
+_DEPTH_FUSION_RULE = """
+    The rule (include/ctd_hip.h).  depth [B,V,H,W] f32 holds V views of each of B tracks; ray [H*W,3], K [3,3] as for
+    `geometric_loss`; R [B,V,3,3], t [B,V,3] with X_cam = R X_world + t.  A pixel is live when its `valid` entry is
+    nonzero (valid=None: everywhere) and its depth is finite and > 0.  A source view s != r is consistent with the live
+    pixel p of view r when p, projected into s (the geometric projection u = uvd0 / uvd2, rounded to the nearest pixel),
+    lands inside the image on a live pixel q, and q projected back with its own depth lands within max_px pixels of p at a
+    depth z' with |z' - depth| <= max_rel * depth.  count = the number of consistent views, keep = live and
+    count >= min_views, fused = (depth + the z' of the consistent views, ascending) / (1 + count), NaN where not kept."""
+
+
+def _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views, who):
+    ts = [_f32(x, n) for x, n in ((depth, "depth"), (ray, "ray"), (K, "K"), (R, "R"), (t, "t"))]
+    dev = _same_device(*ts)
+    if depth.dim() != 4 or min(depth.shape[1:]) == 0:
+        raise RuntimeError("%s expects depth [B,V,H,W] with V, H, W >= 1" % who)
+    B, V, H, W = depth.shape
+    if V > 64:
+        raise RuntimeError("%s: at most 64 views" % who)
+    if ray.numel() != H * W * 3 or K.numel() != 9 or R.numel() != B * V * 9 or t.numel() != B * V * 3:
+        raise RuntimeError("%s: ray [H*W,3], K [3,3], R [B,V,3,3], t [B,V,3] expected" % who)
+    v = None
+    if valid is not None:
+        _check(valid, "valid", (torch.bool, torch.uint8))
+        if valid.shape != depth.shape:
+            raise RuntimeError("%s: valid must have the shape of depth" % who)
+        _same_device(depth, valid)
+        v = valid.view(torch.uint8)
+    if not all(isinstance(x, numbers.Real) and 0.0 <= x < float("inf") for x in (max_px, max_rel)):
+        raise RuntimeError("%s: max_px and max_rel must be finite numbers >= 0" % who)
+    max_px, max_rel = float(max_px), float(max_rel)
+    if not isinstance(min_views, numbers.Real) or not 0 <= min_views <= 255 or int(min_views) != min_views:
+        raise RuntimeError("%s: min_views must be an integer in [0, 255]" % who)
+    return dev, v, max_px, max_rel, int(min_views)
+
+
+def depth_consistency(depth, ray, K, R, t, valid=None, max_px=1.0, max_rel=0.01, min_views=1):
+    """Additive: which depths of a track's views the other views confirm -> (count uint8, keep uint8, fused f32), each
+    [B,V,H,W].  Not differentiable."""
+    dev, v, max_px, max_rel, min_views = _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views,
+                                                              "depth_consistency")
+    B, V, H, W = depth.shape
+    count = torch.empty(depth.shape, dtype=torch.uint8, device=dev)
+    keep = torch.empty(depth.shape, dtype=torch.uint8, device=dev)
+    fused = torch.empty(depth.shape, dtype=torch.float32, device=dev)
+    if B == 0:
+        return count, keep, fused
+    st = _lib.lib().ctd_depth_consistency_f32(_ptr(depth), _ptr(v), _ptr(ray), _ptr(K), _ptr(R), _ptr(t), max_px, max_rel,
+                                              min_views, _ptr(count), _ptr(keep), _ptr(fused), B, V, H, W, dev.index,
+                                              _stream(dev))
+    _lib.check(st, "depth_consistency")
+    return count, keep, fused
+
+
+def depth_fuse_points(depth, ray, K, R, t, valid=None, max_px=1.0, max_rel=0.01, min_views=1, dedupe=True,
+                      return_maps=False):
+    """Additive: the fused world points of a track's depth maps -> (points [M,3] f32, src [M] int64, n_per_track [B]
+    int64), and (count, keep, fused) of `depth_consistency` behind them with return_maps.  A kept pixel is emitted;
+    with dedupe, only if no earlier view s < r is consistent with it and keeps the pixel it lands on ("first view
+    wins").  point = (fused * ray[p] - t_r) @ R_r, src = the pixel's flat index ((b*V + r)*H + y)*W + x; the points come
+    in ascending src order, so track b's are the n_per_track[b] entries after those of the tracks before it.  The counts
+    are read back once (one synchronisation) to slice the outputs.  Not differentiable."""
+    dev, v, max_px, max_rel, min_views = _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views,
+                                                              "depth_fuse_points")
+    B, V, H, W = depth.shape
+    n = depth.numel()
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    src = torch.empty((n,), dtype=torch.int64, device=dev)
+    n_per_track = torch.zeros((B,), dtype=torch.int64, device=dev)
+    maps = ()
+    if return_maps:
+        maps = (torch.empty(depth.shape, dtype=torch.uint8, device=dev),
+                torch.empty(depth.shape, dtype=torch.uint8, device=dev),
+                torch.empty(depth.shape, dtype=torch.float32, device=dev))
+    if B == 0:
+        return (points, src, n_per_track) + maps
+    mp = [_ptr(m) for m in maps] or [None] * 3
+    L = _lib.lib()
+    ws = _workspace(L.ctd_depth_fuse_workspace_bytes(B, V, H, W), dev)
+    st = L.ctd_depth_fuse_points_f32(_ptr(depth), _ptr(v), _ptr(ray), _ptr(K), _ptr(R), _ptr(t), max_px, max_rel, min_views,
+                                     1 if dedupe else 0, _ptr(points), _ptr(src), _ptr(n_per_track), mp[0], mp[1], mp[2],
+                                     B, V, H, W, _ptr(ws), ws.numel(), dev.index, _stream(dev))
+    _lib.check(st, "depth_fuse_points")
+    m = int(n_per_track.sum().item())
+    return (points[:m], src[:m], n_per_track) + maps
+
+
+depth_consistency.__doc__ += _DEPTH_FUSION_RULE
+depth_fuse_points.__doc__ += _DEPTH_FUSION_RULE
 
 
 # --------------------------------------------------------------------------------------

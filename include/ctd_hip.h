@@ -405,6 +405,77 @@ int ctd_disp_median_f32(const float* disp, const uint8_t* valid, int window, int
                         int frames, int H, int W, int device, void* stream);
 
 /* --------------------------------------------------------------------------------------
+ * Multi-view depth consistency and point-cloud fusion (additive in ABI version 5): the multi-view counterpart of the
+ * validity flags, and the step from the depth maps of a track -- several views of one scene with known poses -- to a
+ * point cloud.  The reference has no counterpart (its co/geometry.py projects single depth maps on the CPU), so the
+ * rules are defined here, bit for bit: they use IEEE f32 add, sub, mul, div, floor and compares only, in the written
+ * association, never contracted to fused multiply-adds.
+ *
+ * Common terms.  depth [B][V][H][W] f32: V views of one track, B tracks.  valid [B][V][H][W] uint8 or NULL (NULL counts
+ * as nonzero everywhere).  ray [H*W][3] and K [3][3] are shared by the call, exactly as ctd_geometric_fwd_f32 takes
+ * them.  Poses R [B][V][3][3], t [B][V][3] in the convention of the geometric loss: X_cam = R X_world + t.  A pixel is
+ * LIVE when its valid byte is nonzero and its depth is finite and greater than 0.
+ * The transform from view a to view b of depth d at pixel q (in-view linear index), in the association of the geometric
+ * loss's forward:
+ *      P_i   = d*ray[q][i] - t_a[i]
+ *      Q_j   = P0*Ra[0][j] + P1*Ra[1][j] + P2*Ra[2][j]
+ *      S_j   = Q0*Rb[j][0] + Q1*Rb[j][1] + Q2*Rb[j][2] + t_b[j]
+ *      uvd_j = S0*K[j][0] + S1*K[j][1] + S2*K[j][2]
+ * and the pixel coordinates are u = uvd0/uvd2, v = uvd1/uvd2 (IEEE division).  This is the geometric projection itself,
+ * NOT the coordinate ctd_geometric_fwd_f32 samples at: that one is normalised with (W-1), (H-1) and un-normalised by
+ * grid_sample with align_corners = False, a quirk of the reference's training loss that has to be kept there for parity
+ * and that a consistency check must not inherit.
+ *
+ * 1. ctd_depth_consistency_f32.  For each reference view r, each live pixel p = (y, x) of it with depth d_r, and each
+ *    source view s != r of the same track:
+ *    a. uvd = transform r -> s of d_r at p; fail unless uvd2 > 0; u1 = uvd0/uvd2, v1 = uvd1/uvd2;
+ *       xs = floorf(u1 + 0.5f), ys = floorf(v1 + 0.5f); fail unless 0 <= xs <= W-1 and 0 <= ys <= H-1 (float compares,
+ *       before any conversion: a NaN fails); fail unless the source pixel q = (ys, xs) of view s is live.  The sampling
+ *       is nearest neighbour on purpose: a bilinear one would mix depths across occlusion edges and holes.
+ *    b. uvd' = transform s -> r of d_s at q; fail unless uvd'2 > 0; u' = uvd'0/uvd'2, v' = uvd'1/uvd'2, z' = uvd'2.
+ *    c. with du = u' - (float)x, dv = v' - (float)y, view s is CONSISTENT with (r, p) iff
+ *         du*du + dv*dv <= max_px*max_px   and   fabsf(z' - d_r) <= max_rel*d_r.
+ *    Outputs, all [B][V][H][W]:
+ *      count (uint8) = the number of consistent source views; 0 for a pixel that is not live
+ *      keep  (uint8) = 1 where the pixel is live and count >= min_views, else 0
+ *      fused (f32)   = acc / (float)(1 + count), where acc starts as d_r and takes acc = acc + z'_s for each consistent
+ *                      view in ascending s; NaN where keep == 0
+ *    V = 1 gives count = 0 everywhere; min_views = 0 keeps exactly the live pixels with fused = depth.
+ * 2. ctd_depth_fuse_points_f32 runs 1 and then decides per pixel whether to emit it:
+ *      dedupe == 0: emit(r, p) = keep(r, p)
+ *      dedupe != 0: keep(r, p), and there is no s < r such that s is consistent with (r, p) and keep(s, q_s(r, p)) holds,
+ *                   q_s(r, p) being the source pixel of step a
+ *    ("first view wins": it removes most duplicates of a surface that several views see; it is a definition, not a
+ *    symmetry claim).  For every emitted pixel, with fused of 1:
+ *      P_i = fused*ray[p][i] - t_r[i];   point_j = P0*R_r[0][j] + P1*R_r[1][j] + P2*R_r[2][j]       (a world point)
+ *      src = ((b*V + r)*H + y)*W + x                                                   (the flat index of the pixel)
+ *    points [M][3] f32 and src [M] int64 are written densely in ascending src order -- tracks one after the other --
+ *    and n_per_track [B] int64 gets the number of points of each track (M = their sum).  The caller provides points and
+ *    src with the capacity B*V*H*W; entries from M on are left as they were.  count, keep and fused of 1 are written
+ *    as well where their pointers are given; each of the three may be NULL.
+ *    Workspace: ctd_depth_fuse_workspace_bytes(B, V, H, W) bytes, 256-byte aligned; its contents on entry, and those of
+ *    the outputs, do not matter.  The compaction is three launches (counts per workgroup, their exclusive scan in one
+ *    workgroup, the scatter); no workgroup waits for another and there are no atomics, so every run gives the same bits.
+ * The inputs are never written; the outputs must not overlap the inputs, each other or the workspace.
+ * Limits: V in [1, 64]; B*V*H*W < 2^31; every H, W >= 1 up to 2^24 (W - 1 and H - 1 are compared in f32); fewer than
+ *   2^24 workgroups per launch, B*V*ceil(W/64)*ceil(H/4) < 2^24 and B*V*ceil(H*W/256) < 2^24, which only a batch of more
+ *   than four million views of under 1024 pixels each can reach (a launch stays below 2^32 threads).
+ * Errors, before any HIP call: CTD_ERR_INVALID_ARG for a negative or non-finite max_px or max_rel, min_views outside
+ *   [0, 255], B < 0, V < 1, H < 1, W < 1, H or W > 2^24, B*V*H*W >= 2^31, a NULL pointer other than valid (and, for the
+ *   fusion, count / keep / fused) or overlapping buffers; CTD_ERR_UNSUPPORTED for V > 64 or 2^24 workgroups and more; CTD_ERR_WORKSPACE for a NULL,
+ *   short or misaligned workspace.  B == 0 is CTD_OK and touches nothing.  The workspace query returns 0 for sizes the
+ *   calls reject (and for B == 0).
+ * -------------------------------------------------------------------------------------- */
+int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
+                              float* fused, int B, int V, int H, int W, int device, void* stream);
+size_t ctd_depth_fuse_workspace_bytes(int B, int V, int H, int W);
+int ctd_depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
+                              int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B,
+                              int V, int H, int W, void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* --------------------------------------------------------------------------------------
  * Local contrast normalisation, fused.  Replaces the op chain of LCN.tforward,
  * model/networks.py:507-533 (ReflectionPad2d + two all-ones Conv2d + 6 elementwise ops).
  *   x [N][1][H][W] -> y = (x-avg)/std, std  (both [N][1][H][W]);  radius < min(H, W)
