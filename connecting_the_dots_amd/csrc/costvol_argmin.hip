@@ -19,6 +19,7 @@
 #include "ctd_costvol_ref.h"
 #include "ctd_internal.h"
 #include "ctd_top2.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -41,7 +42,7 @@ static ArgminLayout argmin_layout(int frames, int H, int W, int D) {
   return l;
 }
 
-size_t costvol_argmin_workspace_bytes(int frames, int H, int W, int D) {
+static size_t costvol_argmin_workspace_bytes(int frames, int H, int W, int D) {
   if (frames <= 0) return 0;
   return argmin_layout(frames, H, W, D).bytes;
 }
@@ -116,9 +117,9 @@ __global__ __launch_bounds__(256) void costvol_argmin_rescore_kernel(const float
   }
 }
 
-int costvol_argmin_f32(const float* im, const float* pat, long pat_frame_stride, int64_t* idx, float* best, int frames,
-                       int H, int W, int D, int bs, int type, float eps, float rerank_rel, void* workspace,
-                       size_t workspace_bytes, hipStream_t stream) {
+static int costvol_argmin_f32(const float* im, const float* pat, long pat_frame_stride, int64_t* idx, float* best,
+                              int frames, int H, int W, int D, int bs, int type, float eps, float rerank_rel,
+                              void* workspace, size_t workspace_bytes, hipStream_t stream) {
   const ArgminLayout l = argmin_layout(frames, H, W, D);
   if (!workspace || workspace_bytes < l.bytes || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
   char* ws = (char*)workspace;
@@ -147,3 +148,33 @@ int costvol_argmin_f32(const float* im, const float* pat, long pat_frame_stride,
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_costvol_argmin_workspace_bytes(int frames, int H, int W, int D, int block_size, int type,
+                                          int per_frame_pattern) {
+  (void)per_frame_pattern;                                                  // (the layout does not depend on it)
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3 || (block_size & 1) == 0) return 0;
+  if (!costvol_rank_supported(frames, H, W, D, block_size)) return 0;
+  return costvol_argmin_workspace_bytes(frames, H, W, D);
+}
+
+int ctd_costvol_argmin_f32(const float* im, const float* pattern, long pattern_frame_stride, int64_t* idx, float* best,
+                           int frames, int H, int W, int D, int block_size, int type, float eps, float rerank_rel,
+                           void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3 || (block_size & 1) == 0 ||
+      pattern_frame_stride < 0 || rerank_rel != rerank_rel)
+    return CTD_ERR_INVALID_ARG;
+  if (pattern_frame_stride != 0 && pattern_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !idx) return CTD_ERR_INVALID_ARG;
+  if (!costvol_rank_supported(frames, H, W, D, block_size)) return CTD_ERR_UNSUPPORTED;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return costvol_argmin_f32(im, pattern, pattern_frame_stride, idx, best, frames, H, W, D, block_size, type, eps,
+                            rerank_rel, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include "ctd_internal.h"
 #include "ctd_photo_tile.h"
 #include "ctd_top2.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -373,7 +374,8 @@ __global__ __launch_bounds__(256) void costvol_census_kernel(const float* __rest
 
 // The launchers: the store instantiation into `cost`, or, given `top`, the ranking one.  A call that is wrong on two
 // counts keeps the status it always had: the tiled launcher checks its grid before the block size, the census one after.
-// `type` arrives validated (0..3, ctd_api.hip); each launcher answers CTD_ERR_INVALID_ARG for the other kernel's types.
+// `type` arrives validated (0..3, by the entry points below and in costvol_argmin.hip); each launcher answers
+// CTD_ERR_INVALID_ARG for the other kernel's types.
 static int launch_tiled(int bs, int type, const float* im, const float* pat, long pat_frame_stride, float* cost,
                         const Top2Planes* top, int frames, int H, int W, int D, float eps, hipStream_t stream) {
   const int n_chunks = ceil_div(D, top ? kRankChunk : kCvChunk);
@@ -422,8 +424,9 @@ static int launch_census(int bs, int type, const float* im, const float* pat, lo
   });
 }
 
-int costvol_fast_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W,
-                     int D, int bs, int type, float eps, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int costvol_fast_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H,
+                            int W, int D, int bs, int type, float eps, void* workspace, size_t workspace_bytes,
+                            hipStream_t stream) {
   // SAD / MSE, block 9: the sum is separable (a replicate-border box filter of |P[r][c - d] - I[r][c]|) -- the all-D
   // pipeline of ncc_alld.hip (costvol_sep.hip), one subtract per output instead of 81; needs the caller's workspace for the padded planes
   if (workspace && costvol_sep_supported(H, W, D, bs, type) && ((uintptr_t)cost) % 16 == 0 &&
@@ -449,3 +452,29 @@ int costvol_rank_f32(const float* im, const float* pat, long pat_frame_stride, c
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_costvol_workspace_bytes(int frames, int H, int W, int D, int block_size, int type, int per_frame_pattern) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3) return 0;
+  if (!costvol_sep_supported(H, W, D, block_size, type)) return 0;          // the other kernels need none
+  return costvol_sep_workspace_bytes(frames, H, W, D, per_frame_pattern != 0);
+}
+
+int ctd_costvol_fast_f32(const float* im, const float* pattern, long pattern_frame_stride, float* cost, int frames, int H,
+                         int W, int D, int block_size, int type, float eps, void* workspace, size_t workspace_bytes,
+                         int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3 || pattern_frame_stride < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !cost) return CTD_ERR_INVALID_ARG;
+  if (pattern_frame_stride != 0 && pattern_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return costvol_fast_f32(im, pattern, pattern_frame_stride, cost, frames, H, W, D, block_size, type, eps, workspace,
+                          workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,45 @@
+// ctd_validate.h -- argument predicates that the C entry points of more than one kernel family share.
+#pragma once
+#include "ctd_common.h"
+
+namespace ctd {
+
+inline bool vol_shape_ok(int frames, int C, int H, int W, int D, int bs) {
+  if (frames < 0 || C <= 0 || H <= 0 || W <= 0 || D <= 0 || bs <= 0) return false;
+  // the reference indexes outputs with int (common_cuda.h:65-66, ext_cpu.cpp:8-9)
+  if ((double)D * H * W >= 2147483648.0) return false;
+  return true;
+}
+
+inline bool photo_shape_ok(int B, int C, int H, int W, int bs, int type) {
+  return B >= 0 && C > 0 && H > 0 && W > 0 && bs > 0 && type >= 0 && type <= 3 &&
+         (double)B * C * H * W < 2147483648.0;                 // int indices in the reference (ext.h:220-235)
+}
+
+inline bool img_shape_ok(int B, int H, int W) {
+  return B > 0 && H > 0 && W > 0 && B <= 65535 && (double)B * H * W < 2147483648.0;
+}
+
+}  // namespace ctd
+
+// ctd_photometric_{fwd,bwd}_<SFX> over the launchers photometric_{fwd,bwd}_<SFX> of the including file
+// (photometric.hip: f32, f64; photometric_fast.hip: fast_f32)
+#define CTD_PHOTO_ENTRY(SFX, T)                                                                                   \
+  int ctd_photometric_fwd_##SFX(const T* es, const T* ta, T* out, int B, int C, int H, int W, int block_size,      \
+                                int type, float eps, int device, void* stream) {                                   \
+    if (!photo_shape_ok(B, C, H, W, block_size, type)) return CTD_ERR_INVALID_ARG;                                 \
+    if (B == 0) return CTD_OK;                                                                                     \
+    if (!es || !ta || !out) return CTD_ERR_INVALID_ARG;                                                            \
+    DeviceGuard g(device);                                                                                         \
+    if (g.status) return g.status;                                                                                 \
+    return photometric_fwd_##SFX(es, ta, out, B, C, H, W, block_size, type, eps, (hipStream_t)stream);             \
+  }                                                                                                                \
+  int ctd_photometric_bwd_##SFX(const T* es, const T* ta, const T* grad_out, T* grad_es, int B, int C, int H,      \
+                                int W, int block_size, int type, float eps, int device, void* stream) {            \
+    if (!photo_shape_ok(B, C, H, W, block_size, type)) return CTD_ERR_INVALID_ARG;                                 \
+    if (B == 0) return CTD_OK;                                                                                     \
+    if (!es || !ta || !grad_out || !grad_es) return CTD_ERR_INVALID_ARG;                                           \
+    DeviceGuard g(device);                                                                                         \
+    if (g.status) return g.status;                                                                                 \
+    return photometric_bwd_##SFX(es, ta, grad_out, grad_es, B, C, H, W, block_size, type, eps, (hipStream_t)stream); \
+  }

@@ -16,7 +16,7 @@
 //   fuse_scatter_kernel -- the chunks again: offset of the workgroup + flags before the lane (ballot), and for a flagged
 //     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
 // Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 
 namespace ctd {
 namespace {
@@ -230,17 +230,18 @@ FuseLayout fuse_layout(int B, int V, int H, int W) {
 
 }  // namespace
 
-bool depth_fusion_supported(int B, int V, int H, int W) {
+static bool depth_fusion_supported(int B, int V, int H, int W) {
   // a launch stays below 2^32 threads: at most 2^24 - 1 workgroups of 256, for the tiles and for the chunks
   const double views = (double)B * V;
   return views * ceil_div(W, 64) * ceil_div(H, 4) < 16777216.0 && views * chunks_of(H, W) < 16777216.0;
 }
 
-size_t depth_fuse_workspace_bytes(int B, int V, int H, int W) { return fuse_layout(B, V, H, W).bytes; }
+static size_t depth_fuse_workspace_bytes(int B, int V, int H, int W) { return fuse_layout(B, V, H, W).bytes; }
 
-int depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
-                          const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
-                          float* fused, int B, int V, int H, int W, hipStream_t stream) {
+static int depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K,
+                                 const float* R, const float* t, float max_px, float max_rel, int min_views,
+                                 uint8_t* count, uint8_t* keep, float* fused, int B, int V, int H, int W,
+                                 hipStream_t stream) {
   const FuseTol tol = {max_px * max_px, max_rel};
   const int tiles_x = ceil_div(W, 64), tiles = tiles_x * ceil_div(H, 4);          // <= H * W, so the grid is < 2^31
   depth_consistency_kernel<<<dim3((unsigned)((long)tiles * B * V)), dim3(256), 0, stream>>>(
@@ -249,10 +250,10 @@ int depth_consistency_f32(const float* depth, const uint8_t* valid, const float*
   return CTD_OK;
 }
 
-int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
-                          const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
-                          int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B, int V,
-                          int H, int W, void* workspace, hipStream_t stream) {
+static int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K,
+                                 const float* R, const float* t, float max_px, float max_rel, int min_views, int dedupe,
+                                 float* points, int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep,
+                                 float* fused, int B, int V, int H, int W, void* workspace, hipStream_t stream) {
   const FuseLayout l = fuse_layout(B, V, H, W);
   char* ws = (char*)workspace;
   if (!keep) keep = (uint8_t*)(ws + l.keep);
@@ -276,3 +277,78 @@ int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float*
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool depth_fusion_sizes_ok(int B, int V, int H, int W) {
+  // H, W <= 2^24: the bounds of the projected pixel are compared in f32, where W - 1 and H - 1 must be exact
+  return B >= 0 && V >= 1 && H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24) &&
+         (double)B * V * H * W < 2147483648.0;
+}
+
+static bool depth_fusion_params_ok(float max_px, float max_rel, int min_views) {
+  const float big = 3.402823466e38f;                                                          // (a NaN fails >=)
+  return max_px >= 0.f && max_px <= big && max_rel >= 0.f && max_rel <= big && min_views >= 0 && min_views <= 255;
+}
+
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+// true when one of the first n_out spans (the buffers a call writes) shares a byte with any other span; NULL spans are absent
+static bool spans_overlap(const Span* s, int n_out, int n) {
+  for (int i = 0; i < n_out; ++i)
+    for (int j = 0; j < n; ++j) {
+      if (j == i || (j < n_out && j < i) || !s[i].p || !s[j].p || !s[i].bytes || !s[j].bytes) continue;
+      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) return true;
+    }
+  return false;
+}
+
+int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, uint8_t* count, uint8_t* keep,
+                              float* fused, int B, int V, int H, int W, int device, void* stream) {
+  if (!depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_params_ok(max_px, max_rel, min_views)) return CTD_ERR_INVALID_ARG;
+  if (!depth || !ray || !K || !R || !t || !count || !keep || !fused) return CTD_ERR_INVALID_ARG;
+  if (V > 64 || !depth_fusion_supported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  const size_t n = (size_t)B * V * H * W, views = (size_t)B * V;
+  const Span s[] = {{count, n}, {keep, n}, {fused, 4 * n}, {depth, 4 * n}, {valid, n}, {ray, 12 * (size_t)H * W},
+                    {K, 36}, {R, 36 * views}, {t, 12 * views}};
+  if (spans_overlap(s, 3, 9)) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return depth_consistency_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, count, keep, fused, B, V, H, W,
+                               (hipStream_t)stream);
+}
+
+size_t ctd_depth_fuse_workspace_bytes(int B, int V, int H, int W) {
+  if (B <= 0 || V > 64 || !depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_supported(B, V, H, W)) return 0;
+  return depth_fuse_workspace_bytes(B, V, H, W);
+}
+
+int ctd_depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
+                              const float* t, float max_px, float max_rel, int min_views, int dedupe, float* points,
+                              int64_t* src, int64_t* n_per_track, uint8_t* count, uint8_t* keep, float* fused, int B,
+                              int V, int H, int W, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_params_ok(max_px, max_rel, min_views)) return CTD_ERR_INVALID_ARG;
+  if (!depth || !ray || !K || !R || !t || !points || !src || !n_per_track) return CTD_ERR_INVALID_ARG;
+  if (V > 64 || !depth_fusion_supported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  const size_t n = (size_t)B * V * H * W, views = (size_t)B * V;
+  const size_t need = ctd_depth_fuse_workspace_bytes(B, V, H, W);
+  const Span s[] = {{points, 12 * n}, {src, 8 * n}, {n_per_track, 8 * (size_t)B}, {count, n}, {keep, n}, {fused, 4 * n},
+                    {workspace, need}, {depth, 4 * n}, {valid, n}, {ray, 12 * (size_t)H * W}, {K, 36}, {R, 36 * views},
+                    {t, 12 * views}};
+  if (spans_overlap(s, 7, 13)) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return depth_fuse_points_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, dedupe, points, src, n_per_track,
+                               count, keep, fused, B, V, H, W, workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

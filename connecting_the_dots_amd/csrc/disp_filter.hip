@@ -19,7 +19,7 @@
 // disp_median_kernel<WIN> -- a 32 x 8 tile with its halo in LDS, dead pixels as NaN; a thread holds its WIN x WIN taps
 //   in registers and selects by counting ranks (ties in window raster order; a NaN tap compares false, so dead taps
 //   never take part).
-#include "ctd_internal.h"
+#include "ctd_common.h"
 
 namespace ctd {
 namespace {
@@ -242,18 +242,18 @@ int launch_median(const float* disp, const uint8_t* valid, float* out, uint8_t* 
 
 }  // namespace
 
-bool disp_filter_supported(int frames, int H, int W) {
+static bool disp_filter_supported(int frames, int H, int W) {
   // one workgroup per (frame, tile) on grid.x; the median's tiles are the smaller ones
   return (double)frames * ceil_div(W, kMW) * ceil_div(H, kMH) < 2147483648.0;
 }
 
-size_t disp_components_workspace_ints(int frames, int H, int W) {   // parent, count, root
+static size_t disp_components_workspace_ints(int frames, int H, int W) {   // parent, count, root
   return 3 * (((size_t)frames * H * W + 3) & ~(size_t)3);
 }
 
-int disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int max_size,
-                        int32_t* label, int32_t* size, uint8_t* keep, int frames, int H, int W, int* workspace,
-                        hipStream_t stream) {
+static int disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int max_size,
+                               int32_t* label, int32_t* size, uint8_t* keep, int frames, int H, int W, int* workspace,
+                               hipStream_t stream) {
   const long plane = (long)H * W, pixels = plane * frames;
   const size_t seg = ((size_t)pixels + 3) & ~(size_t)3;
   int* parent = workspace;
@@ -280,8 +280,8 @@ int disp_components_f32(const float* disp, const uint8_t* valid, float max_diff,
   return CTD_OK;
 }
 
-int disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
-                    int frames, int H, int W, hipStream_t stream) {
+static int disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out,
+                           uint8_t* valid_out, int frames, int H, int W, hipStream_t stream) {
   switch (window) {
     case 3: return launch_median<3>(disp, valid, out, valid_out, frames, H, W, fill_min, stream);
     case 5: return launch_median<5>(disp, valid, out, valid_out, frames, H, W, fill_min, stream);
@@ -291,3 +291,66 @@ int disp_median_f32(const float* disp, const uint8_t* valid, int window, int fil
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool disp_filter_args_ok(int frames, int H, int W) {
+  return frames >= 0 && H > 0 && W > 0 && (double)H * W < 2147483648.0 && (double)frames * H * W < 2147483648.0;
+}
+
+static bool disp_link_args_ok(float max_diff, int connectivity) {
+  return max_diff >= 0.f && (connectivity == 4 || connectivity == 8);                           // (a NaN fails >=)
+}
+
+size_t ctd_disp_components_workspace_bytes(int frames, int H, int W) {
+  if (frames <= 0 || !disp_filter_args_ok(frames, H, W)) return 0;
+  return sizeof(int) * disp_components_workspace_ints(frames, H, W);
+}
+
+static int disp_components_call(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int max_size,
+                                int32_t* label, int32_t* size, uint8_t* keep, int frames, int H, int W, void* workspace,
+                                size_t workspace_bytes, int device, void* stream) {
+  if (frames == 0) return CTD_OK;
+  if (!disp_filter_supported(frames, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < ctd_disp_components_workspace_bytes(frames, H, W) || ((uintptr_t)workspace & 15))
+    return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_components_f32(disp, valid, max_diff, connectivity, max_size, label, size, keep, frames, H, W,
+                             (int*)workspace, (hipStream_t)stream);
+}
+
+int ctd_disp_components_f32(const float* disp, const uint8_t* valid, float max_diff, int connectivity, int32_t* label,
+                            int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes, int device,
+                            void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || !disp_link_args_ok(max_diff, connectivity)) return CTD_ERR_INVALID_ARG;
+  if (!disp || !label || !size) return CTD_ERR_INVALID_ARG;
+  return disp_components_call(disp, valid, max_diff, connectivity, 0, label, size, nullptr, frames, H, W, workspace,
+                              workspace_bytes, device, stream);
+}
+
+int ctd_disp_speckle_f32(const float* disp, const uint8_t* valid, float max_diff, int max_size, int connectivity,
+                         uint8_t* keep, int32_t* size, int frames, int H, int W, void* workspace, size_t workspace_bytes,
+                         int device, void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || !disp_link_args_ok(max_diff, connectivity) || max_size < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (!disp || !keep) return CTD_ERR_INVALID_ARG;
+  return disp_components_call(disp, valid, max_diff, connectivity, max_size, nullptr, size, keep, frames, H, W, workspace,
+                              workspace_bytes, device, stream);
+}
+
+int ctd_disp_median_f32(const float* disp, const uint8_t* valid, int window, int fill_min, float* out, uint8_t* valid_out,
+                        int frames, int H, int W, int device, void* stream) {
+  if (!disp_filter_args_ok(frames, H, W) || (window != 3 && window != 5 && window != 7) || fill_min < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (!disp || !out || !valid_out || out == disp || (const uint8_t*)valid_out == valid) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!disp_filter_supported(frames, H, W)) return CTD_ERR_UNSUPPORTED;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_median_f32(disp, valid, window, fill_min, out, valid_out, frames, H, W, (hipStream_t)stream);
+}
+
+}  // extern "C"

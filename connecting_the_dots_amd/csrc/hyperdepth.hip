@@ -26,7 +26,7 @@
 // over [0, C) and over [0, C) without pos: exactly the first two keys above when at least two classes are non-zero.
 // With counts >= 0 a zero class never beats a non-zero one, so with one non-zero class pos2 is the first zero class
 // (0, or 1 when pos == 0), and with none pos = 0, pos2 = 1 (C >= 2, checked at the boundary).
-#include "ctd_internal.h"
+#include "ctd_common.h"
 
 namespace ctd {
 
@@ -201,17 +201,17 @@ __global__ __launch_bounds__(kHdPix) void hd_eval_kernel(const ctd_hd_tables tab
   }
 }
 
-size_t hyperdepth_lds_bytes(int n_trees, int n_classes) {
+static size_t hyperdepth_lds_bytes(int n_trees, int n_classes) {
   return (size_t)n_trees * kHdPix * 16 + (size_t)n_classes * 4;
 }
 
-long hyperdepth_grid(int N, int H, int W) {
+static long hyperdepth_grid(int N, int H, int W) {
   const long total = (long)H * N * ceil_div(W, kHdPix);
   return (total + 7) / 8 * 8;
 }
 
-int hyperdepth_eval_f32(const ctd_hd_tables& tab, const uint8_t* ims, int N, int H, int W, int row_from, int row_to,
-                        int n_disp_bins, float* out, hipStream_t stream) {
+static int hyperdepth_eval_f32(const ctd_hd_tables& tab, const uint8_t* ims, int N, int H, int W, int row_from,
+                               int row_to, int n_disp_bins, float* out, hipStream_t stream) {
   const int chunks = ceil_div(W, kHdPix);
   const long total = (long)H * N * chunks;
   const long per_xcd = (total + 7) / 8;
@@ -223,3 +223,34 @@ int hyperdepth_eval_f32(const ctd_hd_tables& tab, const uint8_t* ims, int N, int
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_hyperdepth_eval_f32(const ctd_hd_tables* tables, const uint8_t* ims, int N, int H, int W, int row_from,
+                            int row_to, int n_disp_bins, float* out, int device, void* stream) {
+  if (!tables) return CTD_ERR_INVALID_ARG;
+  const ctd_hd_tables t = *tables;
+  if (N < 0 || H < 1 || W < 1 || H >= (1 << 24) || W >= (1 << 24)) return CTD_ERR_INVALID_ARG;
+  if (row_from < 0 || row_from > row_to || row_to > H) return CTD_ERR_INVALID_ARG;
+  if (t.n_trees < 1 || t.n_trees > 16 || t.n_classes < 2 || n_disp_bins < 1 || t.n_nodes < 0 || t.n_leaves < 0 ||
+      t.n_entries < 0 || t.max_depth < 0 || t.n_rows < 0)
+    return CTD_ERR_INVALID_ARG;
+  if (row_from < row_to && (row_from < t.row0 || (long)row_to > (long)t.row0 + t.n_rows)) return CTD_ERR_INVALID_ARG;
+  if (!ims || !out || !t.roots || !t.leaf_off || !t.leaf_sum || (t.n_nodes > 0 && !t.nodes) ||
+      (t.n_entries > 0 && !t.entries))
+    return CTD_ERR_INVALID_ARG;
+  // the kernel reads nodes as int4 pairs, entries as int2, offsets as int64
+  if ((uintptr_t)t.nodes % 16 || (uintptr_t)t.entries % 8 || (uintptr_t)t.leaf_off % 8 || (uintptr_t)t.roots % 4 ||
+      (uintptr_t)t.leaf_sum % 4 || (uintptr_t)out % 4)
+    return CTD_ERR_INVALID_ARG;
+  if (hyperdepth_lds_bytes(t.n_trees, t.n_classes) > 65536) return CTD_ERR_UNSUPPORTED;
+  if (hyperdepth_grid(N, H, W) > 2147483647L) return CTD_ERR_UNSUPPORTED;
+  if (N == 0) return CTD_OK;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return hyperdepth_eval_f32(t, ims, N, H, W, row_from, row_to, n_disp_bins, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

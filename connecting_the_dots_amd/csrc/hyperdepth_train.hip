@@ -19,7 +19,7 @@
 //   4. plan:     one workgroup assigns split / leaf / entry indices in frontier order (deterministic), writes the
 //                ctd_hd_tables records, links every node into its parent and emits the next frontier.
 // A final pass moves the leaf lists from their scratch slots to the packed entries.  Nothing returns to the host.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 
 namespace ctd {
 
@@ -772,22 +772,22 @@ static HdtLayout hdt_layout(const ctd_hd_train_params& p, int R, const int64_t* 
   return L;
 }
 
-size_t hyperdepth_train_workspace_bytes(const ctd_hd_train_params& p, int R, const int64_t* counts,
-                                        long long cap_leaves) {
+static size_t hyperdepth_train_workspace_bytes(const ctd_hd_train_params& p, int R, const int64_t* counts,
+                                               long long cap_leaves) {
   return hdt_layout(p, R, counts).bytes + align_up(12 * (size_t)(cap_leaves > 0 ? cap_leaves : 0), 256);
 }
 
-int hyperdepth_train_count_f32(const float* disps, int N, int H, int W, int row_from, int row_to, int nb,
-                               int64_t* counts, hipStream_t stream) {
+static int hyperdepth_train_count_f32(const float* disps, int N, int H, int W, int row_from, int row_to, int nb,
+                                      int64_t* counts, hipStream_t stream) {
   hipLaunchKernelGGL(hdt_count_kernel, dim3(row_to - row_from), dim3(kTB), 0, stream, disps, N, H, W, row_from, nb,
                      W * nb, (long long*)counts);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }
 
-int hyperdepth_train_f32(const ctd_hd_train_params& p, const int64_t* X, const uint8_t* ims, const float* disps, int N,
-                         int H, int W, int row_from, int row_to, const int64_t* counts, void* ws, size_t ws_bytes,
-                         const ctd_hd_train_out& out, hipStream_t stream) {
+static int hyperdepth_train_f32(const ctd_hd_train_params& p, const int64_t* X, const uint8_t* ims, const float* disps,
+                                int N, int H, int W, int row_from, int row_to, const int64_t* counts, void* ws,
+                                size_t ws_bytes, const ctd_hd_train_out& out, hipStream_t stream) {
   const int R = row_to - row_from;
   const HdtLayout L = hdt_layout(p, R, counts);
   if (ws_bytes < hyperdepth_train_workspace_bytes(p, R, counts, out.cap_leaves)) return CTD_ERR_WORKSPACE;
@@ -865,3 +865,63 @@ int hyperdepth_train_f32(const ctd_hd_train_params& p, const int64_t* X, const u
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool hd_train_shape_ok(int N, int H, int W, int row_from, int row_to, int nb) {
+  if (N < 1 || H < 1 || W < 1 || H >= (1 << 24) || W >= (1 << 24)) return false;
+  if ((long long)N * H * W >= (1ll << 31)) return false;
+  if (row_from < 0 || row_from >= row_to || row_to > H) return false;
+  return nb >= 1 && (long long)W * nb < (1ll << 31);
+}
+
+static bool hd_train_params_ok(const ctd_hd_train_params* p) {
+  return p && p->n_trees >= 1 && p->n_trees <= 16 && p->max_tree_depth >= 0 && p->max_tree_depth <= 24 &&
+         p->n_test_split_functions >= 0 && p->n_test_split_functions < (1 << 20) && p->n_test_thresholds >= 0 &&
+         p->n_test_thresholds < (1 << 16) && p->n_test_samples >= 1 && p->n_test_samples <= 8192 &&
+         p->min_samples_to_split >= 0 && p->min_samples_for_leaf >= 1 && p->n_disp_bins >= 1;
+}
+
+int ctd_hyperdepth_train_count_f32(const float* disps, int N, int H, int W, int row_from, int row_to,
+                                   int n_disp_bins, int64_t* counts, int device, void* stream) {
+  if (!disps || !counts || !hd_train_shape_ok(N, H, W, row_from, row_to, n_disp_bins)) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return hyperdepth_train_count_f32(disps, N, H, W, row_from, row_to, n_disp_bins, counts, (hipStream_t)stream);
+}
+
+size_t ctd_hyperdepth_train_workspace_bytes(const ctd_hd_train_params* params, int n_rows, const int64_t* row_counts,
+                                            int64_t cap_leaves) {
+  if (!hd_train_params_ok(params) || n_rows < 1 || !row_counts || cap_leaves < 0) return 0;
+  for (int r = 0; r < n_rows; ++r)
+    if (row_counts[r] < 0) return 0;
+  return hyperdepth_train_workspace_bytes(*params, n_rows, row_counts, cap_leaves);
+}
+
+int ctd_hyperdepth_train_f32(const ctd_hd_train_params* params, const int64_t* X, int n_x, const uint8_t* ims,
+                             const float* disps, int N, int H, int W, int row_from, int row_to,
+                             const int64_t* row_counts, void* workspace, size_t workspace_bytes,
+                             const ctd_hd_train_out* out, int device, void* stream) {
+  if (!hd_train_params_ok(params) || !X || !ims || !disps || !row_counts || !workspace || !out) return CTD_ERR_INVALID_ARG;
+  if (!hd_train_shape_ok(N, H, W, row_from, row_to, params->n_disp_bins)) return CTD_ERR_INVALID_ARG;
+  if (n_x < params->n_test_samples + 1) return CTD_ERR_INVALID_ARG;
+  const ctd_hd_train_out o = *out;
+  if (!o.roots || !o.leaf_off || !o.leaf_sum || !o.used || o.cap_nodes < 0 || o.cap_leaves < 0 || o.cap_entries < 0 ||
+      (o.cap_nodes > 0 && !o.nodes) || (o.cap_entries > 0 && !o.entries))
+    return CTD_ERR_INVALID_ARG;
+  if ((uintptr_t)o.entries % 8 || (uintptr_t)o.leaf_off % 8 || (uintptr_t)o.used % 8 || (uintptr_t)X % 8 ||
+      (uintptr_t)workspace % 256)
+    return CTD_ERR_INVALID_ARG;
+  for (int r = 0; r < row_to - row_from; ++r)
+    if (row_counts[r] < 0) return CTD_ERR_INVALID_ARG;
+  if (workspace_bytes < hyperdepth_train_workspace_bytes(*params, row_to - row_from, row_counts, o.cap_leaves))
+    return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return hyperdepth_train_f32(*params, X, ims, disps, N, H, W, row_from, row_to, row_counts, workspace,
+                              workspace_bytes, o, (hipStream_t)stream);
+}
+
+}  // extern "C"

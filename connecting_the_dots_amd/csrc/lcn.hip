@@ -12,7 +12,7 @@
 //     avgs = boxs / n;  stds = sqrt(boxs2 / n - avgs*avgs + 1e-6) + eps;  y = (x - avgs) / stds
 // The CPU oracle (oracle/ctd_oracle.c: ctd_oracle_lcn_f32) uses the same order, so the
 // two agree bit for bit.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_lcn_window.h"
 
 namespace ctd {
@@ -317,7 +317,8 @@ __global__ __launch_bounds__(256) void lcn_fast_kernel(const float* __restrict__
 #define CTD_LCN_FAST_TH 16
 #endif
 
-int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream) {
+static int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps,
+                        hipStream_t stream) {
   // radius 7 only: with the tile-mean centring radii 1 .. 6 failed the float64 rule of tests/test_lcn_f64_gpu.py (a dark
   // window in a tile with bright rows cancels against the bright level: std up to 12 x the bound at radii 1 .. 5; flat
   // quantised levels 1.28 x the stock-f32 error at radius 6), so those radii are CTD_ERR_UNSUPPORTED (callers run
@@ -331,7 +332,8 @@ int lcn_fast_f32(const float* x, float* y, float* stds, int N, int H, int W, int
   return CTD_OK;
 }
 
-int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps, hipStream_t stream) {
+static int lcn_f32(const float* x, float* y, float* stds, int N, int H, int W, int radius, float eps,
+                   hipStream_t stream) {
   const int TRr = kLcnTH + 2 * radius, TCc = kLcnTW + 2 * radius;
   size_t lds = sizeof(double) * 2 * TRr * kLcnTW + sizeof(float) * (size_t)TRr * TCc;
   if (lds > 160 * 1024) return CTD_ERR_UNSUPPORTED;
@@ -387,8 +389,8 @@ __global__ __launch_bounds__(256) void lcn_datagen_kernel(const float* __restric
   }
 }
 
-int lcn_datagen_f32(const float* img, float* out, float* out_std, int N, int H, int W, int ks, float eps,
-                    hipStream_t stream) {
+static int lcn_datagen_f32(const float* img, float* out, float* out_std, int N, int H, int W, int ks, float eps,
+                           hipStream_t stream) {
   const size_t lds = sizeof(float) * (size_t)(kLdTW + 2 * ks) * (kLdTH + 2 * ks);
   if (lds > 64 * 1024) return CTD_ERR_UNSUPPORTED;
   dim3 grid(ceil_div(W, kLdTW), ceil_div(H, kLdTH), N);
@@ -398,3 +400,41 @@ int lcn_datagen_f32(const float* img, float* out, float* out_std, int N, int H, 
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_lcn_f32(const float* x, float* y, float* std_out, int N, int H, int W, int radius, float eps, int device,
+                void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || radius < 0 || radius >= H || radius >= W || (double)H * W >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!x || !y || !std_out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return lcn_f32(x, y, std_out, N, H, W, radius, eps, (hipStream_t)stream);
+}
+
+int ctd_lcn_fast_f32(const float* x, float* y, float* std_out, int N, int H, int W, int radius, float eps, int device,
+                     void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || radius < 0 || radius >= H || radius >= W || (double)H * W >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!x || !y || !std_out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return lcn_fast_f32(x, y, std_out, N, H, W, radius, eps, (hipStream_t)stream);
+}
+
+int ctd_lcn_datagen_f32(const float* img, float* out, float* out_std, int N, int H, int W, int kernel_size, float eps,
+                        int device, void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || kernel_size < 0 || N > 65535) return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!img || !out || !out_std) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return lcn_datagen_f32(img, out, out_std, N, H, W, kernel_size, eps, (hipStream_t)stream);
+}
+
+}  // extern "C"

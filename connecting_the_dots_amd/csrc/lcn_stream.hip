@@ -32,7 +32,7 @@
 // construction: the image constant is 0 here) with the same listing rule.
 #include <cstdlib>
 
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_prepass.h"
 #include "ctd_wave.h"
 

@@ -7,7 +7,8 @@
 //   * ProjectionDepthSimilarityLoss.fwd networks.py:416-498   (2 bmm, normalise, grid_sample, abs, clamp, mean)
 // The reference's arithmetic here is ATen's (conv / bmm / grid_sample summation orders are unspecified),
 // so parity is by tolerance against vectors captured from the reference modules (tests/golden/losses.npz).
-#include "ctd_internal.h"
+#include "ctd_common.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -90,20 +91,20 @@ __global__ void d2d_idx_kernel(const int64_t* __restrict__ idx, float* __restric
     depth[i] = (1.0f / x) * bf;
   }
 }
-int idx_to_depth_f32(const int64_t* idx, float* depth, long n, float bf, float offset, hipStream_t s) {
+static int idx_to_depth_f32(const int64_t* idx, float* depth, long n, float bf, float offset, hipStream_t s) {
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(d2d_idx_kernel, dim3(blocks), dim3(256), 0, s, idx, depth, n, bf, offset);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }
 
-int disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float bf, hipStream_t s) {
+static int disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float bf, hipStream_t s) {
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(d2d_fwd_kernel, dim3(blocks), dim3(256), 0, s, disp, depth, n, bf);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }
-int disp_to_depth_bwd_f32(const float* disp, const float* go, float* gi, long n, float bf, hipStream_t s) {
+static int disp_to_depth_bwd_f32(const float* disp, const float* go, float* gi, long n, float bf, hipStream_t s) {
   const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipLaunchKernelGGL(d2d_bwd_kernel, dim3(blocks), dim3(256), 0, s, disp, go, gi, n, bf);
   CTD_LAUNCH_CHECK();
@@ -225,14 +226,14 @@ __global__ __launch_bounds__(256) void disparity_loss_bwd2_kernel(const float* _
 
 static long loss_grid_blocks(int B, int H, int W) { return (long)ceil_div(W, 64) * ceil_div(H, 4) * B; }
 
-size_t disparity_loss_workspace_bytes(int B, int H, int W) {
+static size_t disparity_loss_workspace_bytes(int B, int H, int W) {
   size_t partials = align_up(sizeof(float) * (size_t)loss_grid_blocks(B, H, W), 256);
   size_t planes = align_up(sizeof(float) * (size_t)B * H * W, 256);
   return partials + 2 * planes;                       // forward uses the partials, backward the two planes
 }
 
-int disparity_loss_fwd_f32(const float* disp, const float* edge, float* loss, int B, int H, int W, void* ws,
-                           size_t ws_bytes, hipStream_t s) {
+static int disparity_loss_fwd_f32(const float* disp, const float* edge, float* loss, int B, int H, int W, void* ws,
+                                  size_t ws_bytes, hipStream_t s) {
   if (!ws || ws_bytes < disparity_loss_workspace_bytes(B, H, W)) return CTD_ERR_WORKSPACE;
   dim3 grid(ceil_div(W, 64), ceil_div(H, 4), B), block(256);
   float* partials = (float*)ws;
@@ -244,8 +245,8 @@ int disparity_loss_fwd_f32(const float* disp, const float* edge, float* loss, in
   return CTD_OK;
 }
 
-int disparity_loss_bwd_f32(const float* disp, const float* edge, const float* grad_loss, float* grad_disp,
-                           float* grad_edge, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s) {
+static int disparity_loss_bwd_f32(const float* disp, const float* edge, const float* grad_loss, float* grad_disp,
+                                  float* grad_edge, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s) {
   if (!ws || ws_bytes < disparity_loss_workspace_bytes(B, H, W)) return CTD_ERR_WORKSPACE;
   dim3 grid(ceil_div(W, 64), ceil_div(H, 4), B), block(256);
   size_t partials = align_up(sizeof(float) * (size_t)loss_grid_blocks(B, H, W), 256);
@@ -531,13 +532,14 @@ __global__ __launch_bounds__(256) void geometric_bwd_kernel(const float* __restr
   grad_depth0[plane + q] = accumulate0 ? grad_depth0[plane + q] + gdep : gdep;
 }
 
-size_t geometric_workspace_bytes(int B, int H, int W) {
+static size_t geometric_workspace_bytes(int B, int H, int W) {
   return align_up(sizeof(float) * (size_t)loss_grid_blocks(B, H, W), 256);
 }
 
-int geometric_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
-                      const float* t0, const float* R1, const float* t1, float* loss, int accumulate, int B, int H,
-                      int W, float clamp, void* ws, size_t ws_bytes, hipStream_t s) {
+static int geometric_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K,
+                             const float* R0, const float* t0, const float* R1, const float* t1, float* loss,
+                             int accumulate, int B, int H, int W, float clamp, void* ws, size_t ws_bytes,
+                             hipStream_t s) {
   if (!ws || ws_bytes < geometric_workspace_bytes(B, H, W)) return CTD_ERR_WORKSPACE;
   dim3 grid(ceil_div(W, 64), ceil_div(H, 4), B), block(256);
   hipLaunchKernelGGL(geometric_fwd_kernel, grid, block, 0, s, depth0, depth1, ray, K, R0, t0, R1, t1, (float*)ws, H, W,
@@ -549,9 +551,10 @@ int geometric_fwd_f32(const float* depth0, const float* depth1, const float* ray
   return CTD_OK;
 }
 
-int geometric_sym_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
-                          const float* t0, const float* R1, const float* t1, float* loss, int B, int H, int W, float clamp,
-                          void* ws, size_t ws_bytes, unsigned* ticket, hipStream_t s) {
+static int geometric_sym_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K,
+                                 const float* R0, const float* t0, const float* R1, const float* t1, float* loss, int B,
+                                 int H, int W, float clamp, void* ws, size_t ws_bytes, unsigned* ticket,
+                                 hipStream_t s) {
   // (one f64 per unit of four tiles: 2 x ceil(n_dir / 4) x 8 bytes <= the 2 x n_dir x 4 bytes of the tiles' f32 partials + 64)
   if (!ws || ws_bytes < geometric_workspace_bytes(2 * B, H, W) || ((uintptr_t)ws & 7) || !ticket) return CTD_ERR_WORKSPACE;
   const long n_dir = (long)ceil_div(W, 64) * ceil_div(H, 4) * B;
@@ -568,9 +571,10 @@ int geometric_sym_fwd_f32(const float* depth0, const float* depth1, const float*
   return CTD_OK;
 }
 
-int geometric_bwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
-                      const float* t0, const float* R1, const float* t1, const float* grad_loss, float* grad_depth0,
-                      int accumulate0, float* grad_depth1, int B, int H, int W, float clamp, hipStream_t s) {
+static int geometric_bwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K,
+                             const float* R0, const float* t0, const float* R1, const float* t1, const float* grad_loss,
+                             float* grad_depth0, int accumulate0, float* grad_depth1, int B, int H, int W, float clamp,
+                             hipStream_t s) {
   dim3 grid(ceil_div(W, 64), ceil_div(H, 4), B), block(256);
   hipLaunchKernelGGL(geometric_bwd_kernel, grid, block, 0, s, depth0, depth1, ray, K, R0, t0, R1, t1, grad_loss,
                      (float)(1.0 / ((double)B * H * W)), grad_depth0, grad_depth1, H, W, clamp, accumulate0);
@@ -579,3 +583,101 @@ int geometric_bwd_f32(const float* depth0, const float* depth1, const float* ray
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_disp_to_depth_fwd_f32(const float* disp, float* depth, long n, float baseline_focal, int device, void* stream) {
+  if (n < 0) return CTD_ERR_INVALID_ARG;
+  if (n == 0) return CTD_OK;
+  if (!disp || !depth) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_to_depth_fwd_f32(disp, depth, n, baseline_focal, (hipStream_t)stream);
+}
+
+int ctd_idx_to_depth_f32(const int64_t* idx, float* depth, long n, float baseline_focal, float disp_offset, int device,
+                         void* stream) {
+  if (n < 0) return CTD_ERR_INVALID_ARG;
+  if (n == 0) return CTD_OK;
+  if (!idx || !depth) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return idx_to_depth_f32(idx, depth, n, baseline_focal, disp_offset, (hipStream_t)stream);
+}
+
+int ctd_disp_to_depth_bwd_f32(const float* disp, const float* grad_depth, float* grad_disp, long n,
+                              float baseline_focal, int device, void* stream) {
+  if (n < 0) return CTD_ERR_INVALID_ARG;
+  if (n == 0) return CTD_OK;
+  if (!disp || !grad_depth || !grad_disp) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disp_to_depth_bwd_f32(disp, grad_depth, grad_disp, n, baseline_focal, (hipStream_t)stream);
+}
+
+size_t ctd_disparity_loss_workspace_bytes(int B, int H, int W) {
+  return img_shape_ok(B, H, W) ? disparity_loss_workspace_bytes(B, H, W) : 0;
+}
+
+int ctd_disparity_loss_fwd_f32(const float* disp, const float* edge, float* loss, int B, int H, int W, void* workspace,
+                               size_t workspace_bytes, int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || !disp || !loss) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disparity_loss_fwd_f32(disp, edge, loss, B, H, W, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ctd_disparity_loss_bwd_f32(const float* disp, const float* edge, const float* grad_loss, float* grad_disp,
+                               float* grad_edge, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                               int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || !disp || !grad_loss || !grad_disp) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return disparity_loss_bwd_f32(disp, edge, grad_loss, grad_disp, grad_edge, B, H, W, workspace, workspace_bytes,
+                                (hipStream_t)stream);
+}
+
+size_t ctd_geometric_workspace_bytes(int B, int H, int W) {
+  return img_shape_ok(B, H, W) ? geometric_workspace_bytes(B, H, W) : 0;
+}
+
+int ctd_geometric_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
+                          const float* t0, const float* R1, const float* t1, float* loss, int accumulate, int B, int H,
+                          int W, float clamp, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || H < 2 || W < 2 || !depth0 || !depth1 || !ray || !K || !R0 || !t0 || !R1 || !t1 || !loss)
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return geometric_fwd_f32(depth0, depth1, ray, K, R0, t0, R1, t1, loss, accumulate, B, H, W, clamp, workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
+
+int ctd_geometric_sym_fwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
+                              const float* t0, const float* R1, const float* t1, float* loss, int B, int H, int W,
+                              float clamp, void* workspace, size_t workspace_bytes, unsigned* ticket, int device,
+                              void* stream) {
+  if (!img_shape_ok(B, H, W) || H < 2 || W < 2 || !depth0 || !depth1 || !ray || !K || !R0 || !t0 || !R1 || !t1 || !loss ||
+      !ticket)
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return geometric_sym_fwd_f32(depth0, depth1, ray, K, R0, t0, R1, t1, loss, B, H, W, clamp, workspace, workspace_bytes,
+                               ticket, (hipStream_t)stream);
+}
+
+int ctd_geometric_bwd_f32(const float* depth0, const float* depth1, const float* ray, const float* K, const float* R0,
+                          const float* t0, const float* R1, const float* t1, const float* grad_loss,
+                          float* grad_depth0, int accumulate0, float* grad_depth1, int B, int H, int W, float clamp,
+                          int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || H < 2 || W < 2 || !depth0 || !depth1 || !ray || !K || !R0 || !t0 || !R1 || !t1 ||
+      !grad_loss || !grad_depth0 || !grad_depth1)
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return geometric_bwd_f32(depth0, depth1, ray, K, R0, t0, R1, t1, grad_loss, grad_depth0, accumulate0, grad_depth1, B,
+                           H, W, clamp, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -37,6 +37,7 @@
 #include "ctd_costvol_ref.h"
 #include "ctd_internal.h"
 #include "ctd_ncc_point.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -256,11 +257,15 @@ __global__ __launch_bounds__(256) void validity_flag_kernel(const int64_t* __res
   if ((diff < 0 ? -diff : diff) <= (int64_t)lr_tol) flags[p] = (uint8_t)(fl | 2);
 }
 
-bool match_validity_supported(int frames, int H, int W) {
+struct ValidityLayout {                        // workspace of the *_validity calls (byte offsets; ctd_hip.h documents it)
+  size_t counters, pix_list, col_list, vol, inner, bytes;
+};
+
+static bool match_validity_supported(int frames, int H, int W) {
   return H <= 65535 && frames <= 65535 && (double)frames * H * W < 4294967296.0;
 }
 
-ValidityLayout validity_layout(int frames, int H, int W, int D, size_t inner_bytes) {
+static ValidityLayout validity_layout(int frames, int H, int W, int D, size_t inner_bytes) {
   const size_t P = (size_t)frames * H * W;
   ValidityLayout l;
   l.counters = 0;
@@ -272,9 +277,9 @@ ValidityLayout validity_layout(int frames, int H, int W, int D, size_t inner_byt
   return l;
 }
 
-int match_validity_scan_f32(const float* vol, bool maximise, bool fast, const int64_t* idx, uint8_t* flags,
-                            int64_t* idx_r, float* gap, int frames, int D, int H, int W, float min_gap,
-                            unsigned* counters, unsigned* pix_list, unsigned* col_list, hipStream_t stream) {
+static int match_validity_scan_f32(const float* vol, bool maximise, bool fast, const int64_t* idx, uint8_t* flags,
+                                   int64_t* idx_r, float* gap, int frames, int D, int H, int W, float min_gap,
+                                   unsigned* counters, unsigned* pix_list, unsigned* col_list, hipStream_t stream) {
   const dim3 grid(ceil_div(W, 256), H, frames), block(256);
   auto kern = maximise ? (fast ? validity_scan_kernel<true, true> : validity_scan_kernel<true, false>)
                        : (fast ? validity_scan_kernel<false, true> : validity_scan_kernel<false, false>);
@@ -284,10 +289,10 @@ int match_validity_scan_f32(const float* vol, bool maximise, bool fast, const in
   return CTD_OK;
 }
 
-int match_validity_rescore_f32(int family, const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
-                               uint8_t* flags, int64_t* idx_r, float* gap, int frames, int H, int W, int D, int bs,
-                               float eps, float min_gap, const unsigned* counters, const unsigned* pix_list,
-                               const unsigned* col_list, hipStream_t stream) {
+static int match_validity_rescore_f32(int family, const float* in0, const float* in1, long in1_frame_stride,
+                                      const int64_t* idx, uint8_t* flags, int64_t* idx_r, float* gap, int frames, int H,
+                                      int W, int D, int bs, float eps, float min_gap, const unsigned* counters,
+                                      const unsigned* pix_list, const unsigned* col_list, hipStream_t stream) {
   const long wgs_needed = ((long)frames * H * W * 2 + 3) / 4;      // four wavefronts per workgroup, an item each
   const unsigned grid = (unsigned)(wgs_needed < 4L * device_cu_count() ? wgs_needed : 4L * device_cu_count());
 #define CTD_VAL_RESCORE(FAM)                                                                                         \
@@ -305,8 +310,8 @@ int match_validity_rescore_f32(int family, const float* in0, const float* in1, l
   return CTD_OK;
 }
 
-int match_validity_flags(const int64_t* idx, const int64_t* idx_r, uint8_t* flags, int frames, int H, int W, int lr_tol,
-                         hipStream_t stream) {
+static int match_validity_flags(const int64_t* idx, const int64_t* idx_r, uint8_t* flags, int frames, int H, int W,
+                                int lr_tol, hipStream_t stream) {
   const long P = (long)frames * H * W;
   hipLaunchKernelGGL(validity_flag_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, idx, idx_r, flags, P,
                      lr_tol);
@@ -315,3 +320,125 @@ int match_validity_flags(const int64_t* idx, const int64_t* idx_r, uint8_t* flag
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool validity_args_ok(int lr_tol, float min_gap) { return lr_tol >= 0 && min_gap >= 0.f; }   // (a NaN fails >=)
+static bool validity_block_fast(int bs) { return bs == 3 || bs == 5 || bs == 7 || bs == 9; }
+
+int ctd_match_validity_f32(const float* vol, int maximise, const int64_t* idx, uint8_t* flags, int64_t* idx_r, float* gap,
+                           int frames, int D, int H, int W, int lr_tol, float min_gap, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, 1) || !validity_args_ok(lr_tol, min_gap)) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!vol || !idx || !flags || !idx_r || !gap) return CTD_ERR_INVALID_ARG;
+  if (!match_validity_supported(frames, H, W)) return CTD_ERR_UNSUPPORTED;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  const hipStream_t hs = (hipStream_t)stream;
+  int st = match_validity_scan_f32(vol, maximise != 0, false, idx, flags, idx_r, gap, frames, D, H, W, min_gap, nullptr,
+                                   nullptr, nullptr, hs);
+  if (st) return st;
+  return match_validity_flags(idx, idx_r, flags, frames, H, W, lr_tol, hs);
+}
+
+// scan of the volume in the workspace, exact re-scoring of the listed items (fast volumes), flag pass
+static int validity_finish(const ValidityLayout& l, void* workspace, bool fast, int family, const float* in0,
+                           const float* in1, long in1_frame_stride, const int64_t* idx, uint8_t* flags, int64_t* idx_r,
+                           float* gap, int frames, int H, int W, int D, int bs, float eps, int lr_tol, float min_gap,
+                           hipStream_t hs) {
+  char* ws = (char*)workspace;
+  unsigned* counters = (unsigned*)(ws + l.counters);
+  unsigned* pix_list = (unsigned*)(ws + l.pix_list);
+  unsigned* col_list = (unsigned*)(ws + l.col_list);
+  int st = match_validity_scan_f32((const float*)(ws + l.vol), family == 4, fast, idx, flags, idx_r, gap, frames, D, H, W,
+                                   min_gap, counters, pix_list, col_list, hs);
+  if (st) return st;
+  if (fast) {
+    st = match_validity_rescore_f32(family, in0, in1, in1_frame_stride, idx, flags, idx_r, gap, frames, H, W, D, bs, eps,
+                                    min_gap, counters, pix_list, col_list, hs);
+    if (st) return st;
+  }
+  return match_validity_flags(idx, idx_r, flags, frames, H, W, lr_tol, hs);
+}
+
+static bool xcorrvol_validity_algo_ok(int C, int D, int bs, int algo) {
+  return algo == CTD_NCC_EXACT || (C == 1 && validity_block_fast(bs) && D <= 512);
+}
+
+size_t ctd_xcorrvol_validity_workspace_bytes(int frames, int C, int H, int W, int D, int block_size, int algo) {
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || frames == 0 || (algo != CTD_NCC_EXACT && algo != CTD_NCC_FAST)) return 0;
+  if (!match_validity_supported(frames, H, W) || !xcorrvol_validity_algo_ok(C, D, block_size, algo)) return 0;
+  return validity_layout(frames, H, W, D, ctd_xcorrvol_workspace_bytes(frames, C, H, W, D, block_size, algo)).bytes;
+}
+
+int ctd_xcorrvol_validity_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                              uint8_t* flags, int64_t* idx_r, float* gap, int frames, int C, int H, int W, int D,
+                              int block_size, int algo, int lr_tol, float min_gap, void* workspace,
+                              size_t workspace_bytes, int device, void* stream) {
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || !validity_args_ok(lr_tol, min_gap) ||
+      (algo != CTD_NCC_EXACT && algo != CTD_NCC_FAST))
+    return CTD_ERR_INVALID_ARG;
+  if (in1_frame_stride != 0 && in1_frame_stride != (long)C * H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !idx || !flags || !idx_r || !gap) return CTD_ERR_INVALID_ARG;
+  if (!match_validity_supported(frames, H, W) || !xcorrvol_validity_algo_ok(C, D, block_size, algo)) return CTD_ERR_UNSUPPORTED;
+  const ValidityLayout l = validity_layout(frames, H, W, D, ctd_xcorrvol_workspace_bytes(frames, C, H, W, D, block_size, algo));
+  if (!workspace || workspace_bytes < l.bytes || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  const hipStream_t hs = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  CTD_HIP_TRY(hipMemsetAsync(ws + l.counters, 0, 2 * sizeof(unsigned), hs));
+  int st = ctd_xcorrvol_f32(in0, in1, in1_frame_stride, (float*)(ws + l.vol), frames, C, H, W, D, block_size, algo,
+                            ws + l.inner, l.bytes - l.inner, -1, stream);
+  if (st) return st;
+  return validity_finish(l, workspace, algo == CTD_NCC_FAST, 4, in0, in1, in1_frame_stride, idx, flags, idx_r, gap, frames,
+                         H, W, D, block_size, 0.f, lr_tol, min_gap, hs);
+}
+
+static bool costvol_validity_algo_ok(int frames, int D, int bs, int algo) {
+  return algo == CTD_NCC_FAST ? validity_block_fast(bs) : (long)frames * D <= 65535;   // (the grid of ctd_costvol_f32)
+}
+
+size_t ctd_costvol_validity_workspace_bytes(int frames, int H, int W, int D, int block_size, int type, int algo,
+                                            int per_frame_pattern) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || frames == 0 || type < 0 || type > 3 ||
+      (algo != CTD_NCC_EXACT && algo != CTD_NCC_FAST))
+    return 0;
+  if (!match_validity_supported(frames, H, W) || !costvol_validity_algo_ok(frames, D, block_size, algo)) return 0;
+  const size_t inner = algo == CTD_NCC_FAST ? ctd_costvol_workspace_bytes(frames, H, W, D, block_size, type, per_frame_pattern) : 0;
+  return validity_layout(frames, H, W, D, inner).bytes;
+}
+
+int ctd_costvol_validity_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
+                             uint8_t* flags, int64_t* idx_r, float* gap, int frames, int H, int W, int D, int block_size,
+                             int type, float eps, int algo, int lr_tol, float min_gap, void* workspace,
+                             size_t workspace_bytes, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3 || !validity_args_ok(lr_tol, min_gap) ||
+      (algo != CTD_NCC_EXACT && algo != CTD_NCC_FAST))
+    return CTD_ERR_INVALID_ARG;
+  if (pattern_frame_stride != 0 && pattern_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !idx || !flags || !idx_r || !gap) return CTD_ERR_INVALID_ARG;
+  if (!match_validity_supported(frames, H, W) || !costvol_validity_algo_ok(frames, D, block_size, algo)) return CTD_ERR_UNSUPPORTED;
+  const bool fast = algo == CTD_NCC_FAST;
+  const size_t inner = fast ? ctd_costvol_workspace_bytes(frames, H, W, D, block_size, type, pattern_frame_stride != 0) : 0;
+  const ValidityLayout l = validity_layout(frames, H, W, D, inner);
+  if (!workspace || workspace_bytes < l.bytes || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  const hipStream_t hs = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  CTD_HIP_TRY(hipMemsetAsync(ws + l.counters, 0, 2 * sizeof(unsigned), hs));
+  float* vol = (float*)(ws + l.vol);
+  int st = fast ? ctd_costvol_fast_f32(im, pattern, pattern_frame_stride, vol, frames, H, W, D, block_size, type, eps,
+                                       inner ? ws + l.inner : nullptr, inner, -1, stream)
+                : ctd_costvol_f32(im, pattern, pattern_frame_stride, vol, frames, H, W, D, block_size, type, eps, -1, stream);
+  if (st) return st;
+  return validity_finish(l, workspace, fast, type, im, pattern, pattern_frame_stride, idx, flags, idx_r, gap, frames, H, W, D,
+                         block_size, eps, lr_tol, min_gap, hs);
+}
+
+}  // extern "C"

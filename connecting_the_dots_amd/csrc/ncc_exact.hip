@@ -18,6 +18,7 @@
 // >= 243 ops per output for bs = 9); the HBM-roofline kernel is ncc_fast.hip.
 #include "ctd_internal.h"
 #include "ctd_ncc_point.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -404,7 +405,7 @@ static int dispatch_exact(int bs, const float* in0, const float* in1, long s1, f
 
 static bool exact_has_tiled(int bs) { return bs == 3 || bs == 5 || bs == 7 || bs == 9; }
 
-// entry points used by ctd_api.hip -------------------------------------------------
+// launchers behind the C entry points (below, and the f32 ones in ncc_fast.hip) ----------
 size_t ncc_exact_workspace_bytes(int frames, int C, int H, int W, int D, int bs, bool per_frame_pattern) {
   // worst case over the f32 kernels and the generic f64 one (the caller sizes one workspace per call)
   const size_t g = generic_workspace_bytes<double>(frames, C, H, W, D, per_frame_pattern);
@@ -424,8 +425,8 @@ int ncc_exact_f32(const float* in0, const float* in1, long in1_frame_stride, flo
   return launch_generic<float>(in0, in1, in1_frame_stride, out, frames, C, H, W, D, bs, workspace, workspace_bytes, stream);
 }
 
-int ncc_exact_f64(const double* in0, const double* in1, long in1_frame_stride, double* out, int frames, int C, int H,
-                  int W, int D, int bs, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int ncc_exact_f64(const double* in0, const double* in1, long in1_frame_stride, double* out, int frames, int C,
+                         int H, int W, int D, int bs, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   return launch_generic<double>(in0, in1, in1_frame_stride, out, frames, C, H, W, D, bs, workspace, workspace_bytes, stream);
 }
 
@@ -442,7 +443,8 @@ int ncc_exact_argmax_f32(const float* in0, const float* in1, long in1_frame_stri
                                      stream);
 }
 
-int argmax_disp_f32(const float* vol, int64_t* idx, float* best, int frames, int D, int H, int W, hipStream_t stream) {
+static int argmax_disp_f32(const float* vol, int64_t* idx, float* best, int frames, int D, int H, int W,
+                           hipStream_t stream) {
   long HW = (long)H * W, total = (long)frames * HW;
   hipLaunchKernelGGL(argmax_disp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, vol, idx, best, D,
                      HW, total);
@@ -451,3 +453,31 @@ int argmax_disp_f32(const float* vol, int64_t* idx, float* best, int frames, int
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_xcorrvol_f64(const double* in0, const double* in1, long in1_frame_stride, double* out, int frames, int C,
+                     int H, int W, int D, int block_size, void* workspace, size_t workspace_bytes, int device,
+                     void* stream) {
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || in1_frame_stride < 0) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return ncc_exact_f64(in0, in1, in1_frame_stride, out, frames, C, H, W, D, block_size, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+int ctd_argmax_disp_f32(const float* vol, int64_t* idx, float* best, int frames, int D, int H, int W, int device,
+                        void* stream) {
+  if (frames < 0 || D <= 0 || H <= 0 || W <= 0) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!vol || !idx) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return argmax_disp_f32(vol, idx, best, frames, D, H, W, (hipStream_t)stream);
+}
+
+}  // extern "C"

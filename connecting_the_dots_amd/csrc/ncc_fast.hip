@@ -1,5 +1,7 @@
-// ncc_fast.hip -- host side of the fast NCC path (CTD_NCC_FAST): workspace layout, ranking buffers, the three entry
-// points.  The kernels live one family per file; a call runs them in this order:
+// ncc_fast.hip -- host side of the NCC family: workspace layout, ranking buffers and launch sequences of the fast path
+// (CTD_NCC_FAST), and, at the end, the family's C entry points (ctd_xcorrvol_*, ctd_lcn_xcorrvol_*; those of the exact
+// kernels alone -- ctd_xcorrvol_f64, ctd_argmax_disp_f32 -- are in ncc_exact.hip).  The kernels live one family per
+// file; a fast call runs them in this order:
 //   plain call (ncc_fast_f32, no ranking)
 //     1. ncc_prepass.hip   centred planes + window statistics of frames and pattern, lists of ill-conditioned windows
 //     2. ncc_alld.hip      the volume (block 9, W % 4 == 0, one channel), else ncc_tiles.hip / ncc_t256.hip per channel
@@ -15,8 +17,18 @@
 // Shared declarations: ctd_ncc_fast.h.  Same op as ncc_exact.hip, to |a-b| <= 1e-5*|b| + 1e-6 (ncc_tiles.hip, ncc_fixup.hip).
 #include "ctd_ncc_fast.h"
 #include "ctd_prepass.h"
+#include "ctd_validate.h"
 
 namespace ctd {
+
+// A fused call: the frames arrive raw and `in0` of ncc_fast_f32 is the buffer their LCN goes to (lcn_stream.hip).
+struct FusedLcn {
+  const float* raw;           // [frames][H][W] raw frames
+  float* stds;                // [frames][H][W] LCN deviation output (the LCN output itself is `in0`)
+  int radius;
+  float eps;
+  bool exact;                 // f64 box sums + the reference's f32 tail (the oracle's bits) | f32 sums, v_rcp / v_sqrt tail
+};
 
 static FastWorkspace fast_workspace(void* base, int frames, int C, int H, int W, int D, bool per_frame_pattern) {
   FastWorkspace ws;
@@ -48,12 +60,12 @@ static FastWorkspace fast_workspace(void* base, int frames, int C, int H, int W,
   return ws;
 }
 
-size_t ncc_fast_workspace_bytes(int frames, int C, int H, int W, int D, int bs, bool per_frame_pattern) {
+static size_t ncc_fast_workspace_bytes(int frames, int C, int H, int W, int D, int bs, bool per_frame_pattern) {
   (void)bs;
   return fast_workspace(nullptr, frames, C, H, W, D, per_frame_pattern).bytes;
 }
 
-bool ncc_fast_rank_supported(int C, int H, int W, int D, int bs) {
+static bool ncc_fast_rank_supported(int C, int H, int W, int D, int bs) {
   (void)H;
   return C == 1 && bs == 9 && W % 4 == 0 && D <= 512;      // the all-D kernel, single channel
 }
@@ -82,7 +94,7 @@ static RankPlan rank_plan(void* base, size_t offset, int frames, int H, int W, i
   return rp;
 }
 
-void ncc_fast_rank_offsets(int frames, int H, int W, int D, bool per_frame_pattern, size_t* off) {
+static void ncc_fast_rank_offsets(int frames, int H, int W, int D, bool per_frame_pattern, size_t* off) {
   const FastWorkspace ws = fast_workspace(nullptr, frames, 1, H, W, D, per_frame_pattern);
   const RankPlan rp = rank_plan(nullptr, ws.bytes, frames, H, W, D);
   const AlldPlan ap = alld_plan(frames, H, W, D);
@@ -90,7 +102,7 @@ void ncc_fast_rank_offsets(int frames, int H, int W, int D, bool per_frame_patte
   off[4] = (size_t)ap.n_pass;
 }
 
-size_t ncc_fast_rank_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern) {
+static size_t ncc_fast_rank_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern) {
   const size_t off = fast_workspace(nullptr, frames, 1, H, W, D, per_frame_pattern).bytes;
   return rank_plan(nullptr, off, frames, H, W, D).bytes;
 }
@@ -120,8 +132,8 @@ static PrepassJobs prepass_jobs(const FastWorkspace& ws, const float* in0, const
 // Pattern half of the pre-pass alone (ctd_xcorrvol_pattern_prepare_f32): the pattern's planes, its list of listed windows
 // and run rows stay in `workspace`; calls with `pattern_prepared` on the SAME workspace and shape then skip that half (the
 // reference prepares the pattern once per run, model/exp_synph.py:64-71).  The layout depends on `frames`.
-int ncc_fast_prepare_pattern_f32(const float* in1, long in1_frame_stride, int frames, int C, int H, int W, int D, int bs,
-                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int ncc_fast_prepare_pattern_f32(const float* in1, long in1_frame_stride, int frames, int C, int H, int W, int D,
+                                        int bs, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!fast_shape_supported(frames, C, H, W, D, bs)) return CTD_ERR_UNSUPPORTED;
   const bool per_frame = in1_frame_stride != 0;
   if (per_frame && in1_frame_stride != (long)C * H * W) return CTD_ERR_INVALID_ARG;
@@ -149,9 +161,9 @@ static int launch_volume(float* out, int frames, int C, int H, int W, int D, int
 // nothing is materialised then), ranks every pixel's scores in LDS and writes idx / best / work-list flags itself;
 // *rank comes back filled with the buffers the later passes need and the call STOPS after that kernel -- the caller
 // runs ncc_fast_fixup_ranked (which needs the best scores and indices), then rank_tail_f32.
-int ncc_fast_f32(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int C, int H, int W,
-                 int D, int bs, void* workspace, size_t workspace_bytes, RankPlan* rank, bool pattern_prepared,
-                 hipStream_t stream, const FusedLcn* fused) {
+static int ncc_fast_f32(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int C, int H,
+                        int W, int D, int bs, void* workspace, size_t workspace_bytes, RankPlan* rank,
+                        bool pattern_prepared, hipStream_t stream, const FusedLcn* fused = nullptr) {
   if (!fast_shape_supported(frames, C, H, W, D, bs)) return CTD_ERR_UNSUPPORTED;
   if (fused && (C != 1 || !lcn_stream_supported(H, W, fused->radius, bs))) return CTD_ERR_UNSUPPORTED;
   if (!out && !rank) return CTD_ERR_INVALID_ARG;
@@ -210,11 +222,153 @@ int ncc_fast_f32(const float* in0, const float* in1, long in1_frame_stride, floa
 
 // Second half of a ranked call, after the all-D kernel: fix-up of the listed windows (volume patch when there is one,
 // run values) with every recomputed score held against the `best` / `idx` of its pixel.
-int ncc_fast_fixup_ranked(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int H, int W,
-                          int D, int bs, void* workspace, const RankPlan& rank, const float* best, hipStream_t stream) {
+static int ncc_fast_fixup_ranked(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames,
+                                 int H, int W, int D, int bs, void* workspace, const RankPlan& rank, const float* best,
+                                 hipStream_t stream) {
   const bool per_frame = in1_frame_stride != 0;
   FastWorkspace ws = fast_workspace(workspace, frames, 1, H, W, D, per_frame);
   return launch_fixup(in0, in1, in1_frame_stride, out, frames, 1, H, W, D, bs, ws, per_frame, &rank, best, nullptr, stream);
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_xcorrvol_workspace_bytes(int frames, int C, int H, int W, int D, int block_size, int algo) {
+  if (!vol_shape_ok(frames, C, H, W, D, block_size)) return 0;
+  // worst case over "pattern shared" / "pattern per frame"
+  size_t exact = ncc_exact_workspace_bytes(frames, C, H, W, D, block_size, true);
+  if (algo == CTD_NCC_EXACT) return exact;
+  size_t fast = ncc_fast_workspace_bytes(frames, C, H, W, D, block_size, true);
+  return fast > exact ? fast : exact;
+}
+
+int ctd_xcorrvol_pattern_prepare_f32(const float* in1, long in1_frame_stride, int frames, int C, int H, int W, int D,
+                                     int block_size, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || in1_frame_stride < 0 || frames == 0 || !in1) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return ncc_fast_prepare_pattern_f32(in1, in1_frame_stride, frames, C, H, W, D, block_size, workspace, workspace_bytes,
+                                      (hipStream_t)stream);
+}
+
+int ctd_xcorrvol_f32(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int C, int H,
+                     int W, int D, int block_size, int algo, void* workspace, size_t workspace_bytes, int device,
+                     void* stream) {
+  const bool prepared = (algo & CTD_PATTERN_PREPARED) != 0;
+  algo &= ~CTD_PATTERN_PREPARED;
+  if (prepared && algo != CTD_NCC_FAST) return CTD_ERR_INVALID_ARG;
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || in1_frame_stride < 0) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  if (algo == CTD_NCC_EXACT)
+    return ncc_exact_f32(in0, in1, in1_frame_stride, out, frames, C, H, W, D, block_size, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+  if (algo == CTD_NCC_FAST)
+    return ncc_fast_f32(in0, in1, in1_frame_stride, out, frames, C, H, W, D, block_size, workspace, workspace_bytes,
+                        nullptr, prepared, (hipStream_t)stream);
+  return CTD_ERR_INVALID_ARG;
+}
+
+int ctd_xcorrvol_rank_supported(int C, int H, int W, int D, int block_size) {
+  return vol_shape_ok(1, C, H, W, D, block_size) && ncc_fast_rank_supported(C, H, W, D, block_size) ? 1 : 0;
+}
+
+int ctd_xcorrvol_rank_layout(int frames, int H, int W, int D, int per_frame_pattern, size_t* offsets) {
+  if (!offsets || frames <= 0 || !vol_shape_ok(frames, 1, H, W, D, 9)) return CTD_ERR_INVALID_ARG;
+  ncc_fast_rank_offsets(frames, H, W, D, per_frame_pattern != 0, offsets);
+  return CTD_OK;
+}
+
+size_t ctd_xcorrvol_argmax_workspace_bytes(int frames, int C, int H, int W, int D, int block_size, int algo) {
+  size_t base = ctd_xcorrvol_workspace_bytes(frames, C, H, W, D, block_size, algo);
+  if (base == 0 || algo != CTD_NCC_FAST) return base;
+  // old path: work list behind a 16-byte counter at the start of the workspace
+  size_t need = 16 + sizeof(int64_t) * (size_t)frames * H * W;
+  if (ncc_fast_rank_supported(C, H, W, D, block_size)) need = ncc_fast_rank_workspace_bytes(frames, H, W, D, true);
+  return need > base ? need : base;
+}
+
+int ctd_xcorrvol_argmax_f32(const float* in0, const float* in1, long in1_frame_stride, float* vol_out, int64_t* idx,
+                            float* best, int frames, int C, int H, int W, int D, int block_size, int algo,
+                            float rerank_eps, void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const bool prepared = (algo & CTD_PATTERN_PREPARED) != 0;
+  algo &= ~CTD_PATTERN_PREPARED;
+  if (prepared && algo != CTD_NCC_FAST) return CTD_ERR_INVALID_ARG;
+  if (!vol_shape_ok(frames, C, H, W, D, block_size) || in1_frame_stride < 0) return CTD_ERR_INVALID_ARG;
+  if (C != 1) return CTD_ERR_UNSUPPORTED;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !idx) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  if (algo == CTD_NCC_EXACT)
+    return ncc_exact_argmax_f32(in0, in1, in1_frame_stride, vol_out, idx, best, frames, H, W, D, block_size, workspace,
+                                workspace_bytes, (hipStream_t)stream);
+  if (algo == CTD_NCC_FAST) {
+    if (rerank_eps != rerank_eps) return CTD_ERR_INVALID_ARG;
+    // rerank_eps < 0 (plain argmax of the fast scores, no exact re-scoring) is defined on a materialised volume: the
+    // scores of listed windows exist only there (fix-up pass), so such a call ranks the patched volume in one more pass
+    const bool plain = rerank_eps < 0.f && vol_out;
+    if (!plain && ncc_fast_rank_supported(1, H, W, D, block_size) && ((uintptr_t)vol_out) % 16 == 0) {
+      // ranked inside the all-D volume kernel: {top, runner-up} per pixel in LDS across every disparity; the kernel
+      // writes idx / best / work list itself -- no partial planes, no merge, no pass over the volume
+      RankPlan rp;
+      rp.eps = rerank_eps < 0.f ? 0.f : rerank_eps;                        // (no volume: negative eps means 0)
+      rp.idx = idx;
+      rp.best = best;
+      const hipStream_t hs = (hipStream_t)stream;
+      int st = ncc_fast_f32(in0, in1, in1_frame_stride, vol_out, frames, 1, H, W, D, block_size, workspace,
+                            workspace_bytes, &rp, prepared, hs);       // pre-pass + all-D kernel
+      if (st) return st;
+      st = ncc_fast_fixup_ranked(in0, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, hs);
+      if (st) return st;
+      return rank_tail_f32(rp, vol_out, in0, in1, in1_frame_stride, idx, rp.best, frames, D, H, W, block_size, hs);
+    }
+    if (!vol_out) return CTD_ERR_INVALID_ARG;                              // this shape ranks a materialised volume
+    int st = ncc_fast_f32(in0, in1, in1_frame_stride, vol_out, frames, 1, H, W, D, block_size, workspace,
+                          workspace_bytes, nullptr, prepared, (hipStream_t)stream);
+    if (st) return st;
+    return argmax_rerank_f32(vol_out, in0, in1, in1_frame_stride, idx, best, frames, D, H, W, block_size, rerank_eps,
+                             workspace, workspace_bytes, /*counter_cleared=*/true, (hipStream_t)stream);
+  }
+  return CTD_ERR_INVALID_ARG;
+}
+
+int ctd_lcn_xcorrvol_supported(int H, int W, int D, int radius, int block_size) {
+  return vol_shape_ok(1, 1, H, W, D, block_size) && ncc_fast_rank_supported(1, H, W, D, block_size) &&
+                 lcn_stream_supported(H, W, radius, block_size) ? 1 : 0;
+}
+
+int ctd_lcn_xcorrvol_argmax_f32(const float* raw, float* lcn_out, float* std_out, int radius, float lcn_eps, int lcn_algo,
+                                const float* in1, long in1_frame_stride, float* vol_out, int64_t* idx, float* best,
+                                int frames, int H, int W, int D, int block_size, int algo, float rerank_eps,
+                                void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const bool prepared = (algo & CTD_PATTERN_PREPARED) != 0;
+  algo &= ~CTD_PATTERN_PREPARED;
+  if (algo != CTD_NCC_FAST || (lcn_algo != CTD_LCN_EXACT && lcn_algo != CTD_LCN_FAST)) return CTD_ERR_INVALID_ARG;
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || in1_frame_stride < 0 || radius < 0 || rerank_eps != rerank_eps)
+    return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!raw || !lcn_out || !std_out || !in1 || !idx) return CTD_ERR_INVALID_ARG;
+  if (!ctd_lcn_xcorrvol_supported(H, W, D, radius, block_size) || ((uintptr_t)vol_out) % 16 != 0) return CTD_ERR_UNSUPPORTED;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  const hipStream_t hs = (hipStream_t)stream;
+  const FusedLcn fused = {raw, std_out, radius, lcn_eps, lcn_algo == CTD_LCN_EXACT};
+  RankPlan rp;
+  rp.eps = rerank_eps < 0.f ? 0.f : rerank_eps;             // (as ctd_xcorrvol_argmax_f32 without a plain-argmax pass)
+  rp.idx = idx;
+  rp.best = best;
+  int st = ncc_fast_f32(lcn_out, in1, in1_frame_stride, vol_out, frames, 1, H, W, D, block_size, workspace, workspace_bytes,
+                        &rp, prepared, hs, &fused);           // streaming LCN + statistics, then the all-D kernel
+  if (st) return st;
+  st = ncc_fast_fixup_ranked(lcn_out, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, hs);
+  if (st) return st;
+  return rank_tail_f32(rp, vol_out, lcn_out, in1, in1_frame_stride, idx, rp.best, frames, D, H, W, block_size, hs);
+}
+
+}  // extern "C"

@@ -12,7 +12,6 @@
 #include <cstdint>
 
 #include "ctd_common.h"
-#include "ctd_internal.h"
 
 namespace ctd {
 
@@ -111,14 +110,14 @@ static int nn_launch(const T* in0, const T* in1, long n0, long n1, int64_t* out,
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }
-int nn_f32(const float* in0, const float* in1, long n0, long n1, int64_t* out, hipStream_t s) {
+static int nn_f32(const float* in0, const float* in1, long n0, long n1, int64_t* out, hipStream_t s) {
   return nn_launch(in0, in1, n0, n1, out, s);
 }
-int nn_f64(const double* in0, const double* in1, long n0, long n1, int64_t* out, hipStream_t s) {
+static int nn_f64(const double* in0, const double* in1, long n0, long n1, int64_t* out, hipStream_t s) {
   return nn_launch(in0, in1, n0, n1, out, s);
 }
 
-int crosscheck_i64(const int64_t* in0, const int64_t* in1, long n0, long n1, uint8_t* out, hipStream_t stream) {
+static int crosscheck_i64(const int64_t* in0, const int64_t* in1, long n0, long n1, uint8_t* out, hipStream_t stream) {
   if (n0 == 0) return CTD_OK;
   hipLaunchKernelGGL(crosscheck_kernel, dim3((unsigned)ceil_div(n0, 256L)), dim3(256), 0, stream, in0, in1, n0, n1, out);
   CTD_LAUNCH_CHECK();
@@ -135,13 +134,66 @@ static int proj_nn_launch(const T* xyz0, const T* xyz1, const T* K, long B, long
   CTD_LAUNCH_CHECK();
   return CTD_OK;
 }
-int proj_nn_f32(const float* xyz0, const float* xyz1, const float* K, long B, long H, long W, int patch_size,
-                int64_t* out, hipStream_t s) {
+static int proj_nn_f32(const float* xyz0, const float* xyz1, const float* K, long B, long H, long W, int patch_size,
+                       int64_t* out, hipStream_t s) {
   return proj_nn_launch(xyz0, xyz1, K, B, H, W, patch_size, out, s);
 }
-int proj_nn_f64(const double* xyz0, const double* xyz1, const double* K, long B, long H, long W, int patch_size,
-                int64_t* out, hipStream_t s) {
+static int proj_nn_f64(const double* xyz0, const double* xyz1, const double* K, long B, long H, long W, int patch_size,
+                       int64_t* out, hipStream_t s) {
   return proj_nn_launch(xyz0, xyz1, K, B, H, W, patch_size, out, s);
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_nn_f32(const float* in0, const float* in1, long n0, long n1, int64_t* out, int device, void* stream) {
+  if (n0 < 0 || n1 < 0) return CTD_ERR_INVALID_ARG;
+  if (n0 == 0) return CTD_OK;
+  if (!in0 || !out || (n1 > 0 && !in1)) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return nn_f32(in0, in1, n0, n1, out, (hipStream_t)stream);
+}
+
+int ctd_nn_f64(const double* in0, const double* in1, long n0, long n1, int64_t* out, int device, void* stream) {
+  if (n0 < 0 || n1 < 0) return CTD_ERR_INVALID_ARG;
+  if (n0 == 0) return CTD_OK;
+  if (!in0 || !out || (n1 > 0 && !in1)) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return nn_f64(in0, in1, n0, n1, out, (hipStream_t)stream);
+}
+
+int ctd_crosscheck(const int64_t* in0, const int64_t* in1, long n0, long n1, uint8_t* out, int device, void* stream) {
+  if (n0 < 0 || n1 < 0) return CTD_ERR_INVALID_ARG;
+  if (n0 == 0) return CTD_OK;
+  if (!in0 || !out || (n1 > 0 && !in1)) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return crosscheck_i64(in0, in1, n0, n1, out, (hipStream_t)stream);
+}
+
+int ctd_proj_nn_f32(const float* xyz0, const float* xyz1, const float* K, int B, int H, int W, int patch_size,
+                    int64_t* out, int device, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || patch_size < 0) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  if (!xyz0 || !xyz1 || !K || !out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return proj_nn_f32(xyz0, xyz1, K, B, H, W, patch_size, out, (hipStream_t)stream);
+}
+
+int ctd_proj_nn_f64(const double* xyz0, const double* xyz1, const double* K, int B, int H, int W, int patch_size,
+                    int64_t* out, int device, void* stream) {
+  if (B < 0 || H <= 0 || W <= 0 || patch_size < 0) return CTD_ERR_INVALID_ARG;
+  if (B == 0) return CTD_OK;
+  if (!xyz0 || !xyz1 || !K || !out) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return proj_nn_f64(xyz0, xyz1, K, B, H, W, patch_size, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

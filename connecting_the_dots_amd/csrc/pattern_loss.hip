@@ -8,9 +8,10 @@
 // replicate-clamped taps of pattern_proj, i.e. the sample at the clamped pixel); it is written once because
 // the module returns it.  Backward recomputes the tile, runs the pair-symmetric block-loss backward and
 // applies d pattern_proj / d disp = -(W/(W-1)) * d/dix of the bilinear interpolant (0 where ATen clips).
+#include "ctd_common.h"
 #include "ctd_dispatch.h"
-#include "ctd_internal.h"
 #include "ctd_photo_tile.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -243,13 +244,13 @@ __global__ __launch_bounds__(256) void pattern_loss_multi_bwd_kernel(PatternLeve
                              L.H, L.W, bx * kPTW, by * kPTH, n, eps);
 }
 
-size_t pattern_loss_workspace_bytes(int B, int H, int W) {
+static size_t pattern_loss_workspace_bytes(int B, int H, int W) {
   return sizeof(float2) * (size_t)B * ceil_div(H, kPTH) * ceil_div(W, kPTW);
 }
 
-int pattern_loss_fwd_f32(const float* disp, const float* im, const float* mask, const float* pattern, float* proj,
-                         float* terms, int B, int H, int W, int type, float eps, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
+static int pattern_loss_fwd_f32(const float* disp, const float* im, const float* mask, const float* pattern,
+                                float* proj, float* terms, int B, int H, int W, int type, float eps, void* ws,
+                                size_t ws_bytes, hipStream_t stream) {
   if (!ws || ws_bytes < pattern_loss_workspace_bytes(B, H, W)) return CTD_ERR_WORKSPACE;
   const dim3 grid(ceil_div(W, kPTW), ceil_div(H, kPTH), B);
   float2* partials = (float2*)ws;
@@ -264,9 +265,9 @@ int pattern_loss_fwd_f32(const float* disp, const float* im, const float* mask, 
   });
 }
 
-int pattern_loss_bwd_f32(const float* disp, const float* im, const float* mask, const float* pattern,
-                         const float* terms, const float* grad_val, const float* grad_proj, float* grad_disp, int B,
-                         int H, int W, int type, float eps, hipStream_t stream) {
+static int pattern_loss_bwd_f32(const float* disp, const float* im, const float* mask, const float* pattern,
+                                const float* terms, const float* grad_val, const float* grad_proj, float* grad_disp,
+                                int B, int H, int W, int type, float eps, hipStream_t stream) {
   const dim3 grid(ceil_div(W, kPTW), ceil_div(H, kPTH), B);
   return dispatch_type(type, [&](auto type_c) -> int {
     hipLaunchKernelGGL((pattern_loss_bwd_kernel<decltype(type_c)::value, 9>), grid, dim3(256), 0, stream, disp, im, mask,
@@ -297,15 +298,15 @@ static int build_levels(int n_levels, const ctd_pattern_level* levels, PatternLe
   return CTD_OK;
 }
 
-size_t pattern_loss_multi_workspace_bytes(int n_levels, const ctd_pattern_level* levels) {
+static size_t pattern_loss_multi_workspace_bytes(int n_levels, const ctd_pattern_level* levels) {
   PatternLevelsDev t;
   unsigned total = 0;
   if (build_levels(n_levels, levels, t, total)) return 0;
   return sizeof(float2) * (size_t)total;
 }
 
-int pattern_loss_multi_fwd_f32(int n_levels, const ctd_pattern_level* levels, float* terms, int type, float eps, void* ws,
-                               size_t ws_bytes, hipStream_t stream) {
+static int pattern_loss_multi_fwd_f32(int n_levels, const ctd_pattern_level* levels, float* terms, int type, float eps,
+                                      void* ws, size_t ws_bytes, hipStream_t stream) {
   PatternLevelsDev t;
   unsigned total = 0;
   int st = build_levels(n_levels, levels, t, total);
@@ -326,8 +327,8 @@ int pattern_loss_multi_fwd_f32(int n_levels, const ctd_pattern_level* levels, fl
   return CTD_OK;
 }
 
-int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, const float* terms, const float* grad_vals,
-                               int type, float eps, hipStream_t stream) {
+static int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, const float* terms,
+                                      const float* grad_vals, int type, float eps, hipStream_t stream) {
   PatternLevelsDev t;
   unsigned total = 0;
   int st = build_levels(n_levels, levels, t, total);
@@ -343,3 +344,55 @@ int pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, co
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_pattern_loss_workspace_bytes(int B, int H, int W) {
+  return img_shape_ok(B, H, W) ? pattern_loss_workspace_bytes(B, H, W) : 0;
+}
+
+int ctd_pattern_loss_fwd_f32(const float* disp, const float* im, const float* mask, const float* pattern,
+                             float* pattern_proj, float* terms, int B, int H, int W, int type, float eps,
+                             void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || H < 2 || W < 2 || type < 0 || type > 3) return CTD_ERR_INVALID_ARG;
+  if (!disp || !im || !pattern || !pattern_proj || !terms) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return pattern_loss_fwd_f32(disp, im, mask, pattern, pattern_proj, terms, B, H, W, type, eps, workspace, workspace_bytes,
+                              (hipStream_t)stream);
+}
+
+int ctd_pattern_loss_bwd_f32(const float* disp, const float* im, const float* mask, const float* pattern,
+                             const float* terms, const float* grad_val, const float* grad_proj, float* grad_disp,
+                             int B, int H, int W, int type, float eps, int device, void* stream) {
+  if (!img_shape_ok(B, H, W) || H < 2 || W < 2 || type < 0 || type > 3) return CTD_ERR_INVALID_ARG;
+  if (!disp || !im || !pattern || !terms || !grad_val || !grad_disp) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return pattern_loss_bwd_f32(disp, im, mask, pattern, terms, grad_val, grad_proj, grad_disp, B, H, W, type, eps,
+                              (hipStream_t)stream);
+}
+
+size_t ctd_pattern_loss_multi_workspace_bytes(int n_levels, const ctd_pattern_level* levels) {
+  return pattern_loss_multi_workspace_bytes(n_levels, levels);
+}
+
+int ctd_pattern_loss_multi_fwd_f32(int n_levels, const ctd_pattern_level* levels, float* terms, int type, float eps,
+                                   void* workspace, size_t workspace_bytes, int device, void* stream) {
+  if (!terms || type < 0 || type > 3) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return pattern_loss_multi_fwd_f32(n_levels, levels, terms, type, eps, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ctd_pattern_loss_multi_bwd_f32(int n_levels, const ctd_pattern_level* levels, const float* terms,
+                                   const float* grad_vals, int type, float eps, int device, void* stream) {
+  if (!terms || !grad_vals || type < 0 || type > 3) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return pattern_loss_multi_bwd_f32(n_levels, levels, terms, grad_vals, type, eps, (hipStream_t)stream);
+}
+
+}  // extern "C"

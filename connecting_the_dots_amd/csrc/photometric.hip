@@ -14,8 +14,9 @@
 // visiting (output pixel ascending, tap ascending) -- exactly the order in which the
 // reference's serial CPU loop adds them -- so the result is deterministic, needs no
 // pre-zeroed buffer and no atomics, and is bit-identical to the reference CPU build.
+#include "ctd_common.h"
 #include "ctd_costvol_ref.h"
-#include "ctd_internal.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -178,16 +179,20 @@ static int launch_bwd(const T* es, const T* ta, const T* go, T* gi, int B, int C
   return CTD_OK;
 }
 
-int photometric_fwd_f32(const float* es, const float* ta, float* out, int B, int C, int H, int W, int bs, int type,
-                        float eps, hipStream_t s) { return launch_fwd<float>(es, ta, out, B, C, H, W, bs, type, eps, s); }
-int photometric_fwd_f64(const double* es, const double* ta, double* out, int B, int C, int H, int W, int bs, int type,
-                        float eps, hipStream_t s) { return launch_fwd<double>(es, ta, out, B, C, H, W, bs, type, eps, s); }
-int photometric_bwd_f32(const float* es, const float* ta, const float* go, float* gi, int B, int C, int H, int W,
-                        int bs, int type, float eps, hipStream_t s) {
+static int photometric_fwd_f32(const float* es, const float* ta, float* out, int B, int C, int H, int W, int bs,
+                               int type, float eps, hipStream_t s) {
+  return launch_fwd<float>(es, ta, out, B, C, H, W, bs, type, eps, s);
+}
+static int photometric_fwd_f64(const double* es, const double* ta, double* out, int B, int C, int H, int W, int bs,
+                               int type, float eps, hipStream_t s) {
+  return launch_fwd<double>(es, ta, out, B, C, H, W, bs, type, eps, s);
+}
+static int photometric_bwd_f32(const float* es, const float* ta, const float* go, float* gi, int B, int C, int H, int W,
+                               int bs, int type, float eps, hipStream_t s) {
   return launch_bwd<float>(es, ta, go, gi, B, C, H, W, bs, type, eps, s);
 }
-int photometric_bwd_f64(const double* es, const double* ta, const double* go, double* gi, int B, int C, int H, int W,
-                        int bs, int type, float eps, hipStream_t s) {
+static int photometric_bwd_f64(const double* es, const double* ta, const double* go, double* gi, int B, int C, int H,
+                               int W, int bs, int type, float eps, hipStream_t s) {
   return launch_bwd<double>(es, ta, go, gi, B, C, H, W, bs, type, eps, s);
 }
 
@@ -210,8 +215,8 @@ __global__ __launch_bounds__(256) void costvol_kernel(const float* __restrict__ 
   cost[((long)f * D + d) * HW + (long)h * W + w] = loss;
 }
 
-int costvol_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W, int D,
-                int bs, int type, float eps, hipStream_t stream) {
+static int costvol_f32(const float* im, const float* pat, long pat_frame_stride, float* cost, int frames, int H, int W,
+                       int D, int bs, int type, float eps, hipStream_t stream) {
   dim3 grid(ceil_div(W, 64), ceil_div(H, 4), frames * D), block(256);
   switch (type) {
     case 0: hipLaunchKernelGGL(costvol_kernel<0>, grid, block, 0, stream, im, pat, pat_frame_stride, cost, H, W, D, bs, eps); break;
@@ -225,3 +230,25 @@ int costvol_f32(const float* im, const float* pat, long pat_frame_stride, float*
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+CTD_PHOTO_ENTRY(f32, float)
+CTD_PHOTO_ENTRY(f64, double)
+
+int ctd_costvol_f32(const float* im, const float* pattern, long pattern_frame_stride, float* cost, int frames, int H,
+                    int W, int D, int block_size, int type, float eps, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || type < 0 || type > 3 || pattern_frame_stride < 0 ||
+      (long)frames * D > 65535)
+    return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !cost) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return costvol_f32(im, pattern, pattern_frame_stride, cost, frames, H, W, D, block_size, type, eps,
+                     (hipStream_t)stream);
+}
+
+}  // extern "C"

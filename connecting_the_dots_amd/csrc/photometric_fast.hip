@@ -1,9 +1,10 @@
 // photometric_fast.hip -- tolerance-level (|a-b| <= 1e-5|b| + 1e-6) block photometric loss, f32: the functions of
 // photometric.hip (PhotometricLossForward / PhotometricLossBackward, torchext/ext/ext.h:201-344) on the LDS tile of
 // ctd_photo_tile.h, which also holds the per-pixel arithmetic and the derivation of the atomic-free backward.
+#include "ctd_common.h"
 #include "ctd_dispatch.h"
-#include "ctd_internal.h"
 #include "ctd_photo_tile.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -76,13 +77,21 @@ static int launch_fast(const float* es, const float* ta, const float* go, float*
   });
 }
 
-int photometric_fwd_fast_f32(const float* es, const float* ta, float* out, int B, int C, int H, int W, int bs, int type,
-                             float eps, hipStream_t s) {
+static int photometric_fwd_fast_f32(const float* es, const float* ta, float* out, int B, int C, int H, int W, int bs,
+                                    int type, float eps, hipStream_t s) {
   return launch_fast(es, ta, nullptr, out, B, C, H, W, bs, type, eps, s);
 }
-int photometric_bwd_fast_f32(const float* es, const float* ta, const float* go, float* gi, int B, int C, int H, int W,
-                             int bs, int type, float eps, hipStream_t s) {
+static int photometric_bwd_fast_f32(const float* es, const float* ta, const float* go, float* gi, int B, int C, int H,
+                                    int W, int bs, int type, float eps, hipStream_t s) {
   return launch_fast(es, ta, go, gi, B, C, H, W, bs, type, eps, s);
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+CTD_PHOTO_ENTRY(fast_f32, float)
+
+}  // extern "C"

@@ -11,7 +11,7 @@
 // contraction, so depth, hit face and the projected pattern are bit-identical to the reference CPU build; the
 // shaded ambient image is too whenever the specular weight ks is 0 (the data generator's setting,
 // data/create_syn_data.py:155), otherwise it differs by powf's last bits.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_render.h"
 
 namespace ctd {
@@ -87,10 +87,10 @@ __global__ __launch_bounds__(256) void render_proj_kernel(const float* __restric
   proj_pattern_fetch(proj, pattern, d_alpha, d_beta, pt, porig, pdir, p_t, color, idx);
 }
 
-int render_mesh_proj_f32(const float* verts, const float* colors, const int* faces, int n_faces, const float* cam_p,
-                         int cam_w, int cam_h, const float* proj_p, int proj_w, int proj_h, const float* shader,
-                         const float* pattern, float d_alpha, float d_beta, float* depth, float* color, float* normal,
-                         hipStream_t stream) {
+static int render_mesh_proj_f32(const float* verts, const float* colors, const int* faces, int n_faces,
+                                const float* cam_p, int cam_w, int cam_h, const float* proj_p, int proj_w, int proj_h,
+                                const float* shader, const float* pattern, float d_alpha, float d_beta, float* depth,
+                                float* color, float* normal, hipStream_t stream) {
   const CamDev cam = make_cam(cam_p, cam_w, cam_h), proj = make_cam(proj_p, proj_w, proj_h);
   const long n = (long)cam_w * cam_h;
   hipLaunchKernelGGL(render_proj_kernel, dim3((unsigned)ceil_div(n, 256L)), dim3(256), 0, stream, verts, colors, faces,
@@ -123,9 +123,9 @@ __global__ __launch_bounds__(256) void render_mesh_kernel(const float* __restric
              idx);
 }
 
-int render_mesh_f32(const float* verts, const float* colors, const float* normals, const int* faces, int n_faces,
-                    const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth, float* color, float* normal,
-                    hipStream_t stream) {
+static int render_mesh_f32(const float* verts, const float* colors, const float* normals, const int* faces, int n_faces,
+                           const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth, float* color,
+                           float* normal, hipStream_t stream) {
   const CamDev cam = make_cam(cam_p, cam_w, cam_h);
   const long n = (long)cam_w * cam_h;
   hipLaunchKernelGGL(render_mesh_kernel, dim3((unsigned)ceil_div(n, 256L)), dim3(256), 0, stream, verts, colors, normals,
@@ -135,3 +135,37 @@ int render_mesh_f32(const float* verts, const float* colors, const float* normal
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+int ctd_render_mesh_proj_f32(const float* verts, const float* colors, int n_verts, const int* faces, int n_faces,
+                             const float* cam, int cam_width, int cam_height, const float* proj, int proj_width,
+                             int proj_height, const float* shader, const float* pattern, float d_alpha, float d_beta,
+                             float* depth, float* color, float* normal, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || cam_width <= 0 || cam_height <= 0 || proj_width <= 0 || proj_height <= 0 ||
+      (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!cam || !proj || !shader || !pattern || !color || (n_faces > 0 && (!verts || !colors || !faces)))
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_proj_f32(verts, colors, faces, n_faces, cam, cam_width, cam_height, proj, proj_width, proj_height,
+                              shader, pattern, d_alpha, d_beta, depth, color, normal, (hipStream_t)stream);
+}
+
+int ctd_render_mesh_f32(const float* verts, const float* colors, const float* normals, int n_verts, const int* faces,
+                        int n_faces, const float* cam, int cam_width, int cam_height, const float* shader, float* depth,
+                        float* color, float* normal, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || cam_width <= 0 || cam_height <= 0 || (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!cam || !shader || (n_faces > 0 && (!verts || !faces))) return CTD_ERR_INVALID_ARG;
+  if (n_faces > 0 && ((color && !colors) || ((color || normal) && !normals))) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_f32(verts, colors, normals, faces, n_faces, cam, cam_width, cam_height, shader, depth, color, normal,
+                         (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -55,11 +55,12 @@
 //   costs the visits along their path to the root.
 #include <cstdint>
 
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_render.h"
 
 namespace ctd {
 
+constexpr int kBvhMaxFaces = 1 << 28;
 constexpr int kLeafFaces = 4;       // a node over <= kLeafFaces sorted faces is a leaf
 constexpr int kStack = 64;          // per-lane traversal stack (LDS), entries
 constexpr int kMaxDepth = kStack - 2;
@@ -99,8 +100,8 @@ static WsLayout ws_layout(long n) {
   return W;
 }
 
-size_t mesh_bvh_bytes(long n_faces) { return bvh_layout(n_faces).total; }
-size_t mesh_bvh_workspace_bytes(long n_faces) { return ws_layout(n_faces).total; }
+static size_t mesh_bvh_bytes(long n_faces) { return bvh_layout(n_faces).total; }
+static size_t mesh_bvh_workspace_bytes(long n_faces) { return ws_layout(n_faces).total; }
 
 // ---------------------------------------------------------------------------------------------------- build
 
@@ -330,8 +331,8 @@ __global__ void bvh_header_kernel(int n, int* __restrict__ header, const int4* _
   header[4] = 0;
 }
 
-int mesh_bvh_build_f32(const float* verts, const int* faces, int n, void* bvh, void* ws, int* depth_out,
-                       hipStream_t stream) {
+static int mesh_bvh_build_f32(const float* verts, const int* faces, int n, void* bvh, void* ws, int* depth_out,
+                              hipStream_t stream) {
   const BvhLayout L = bvh_layout(n);
   const WsLayout W = ws_layout(n);
   char* B = (char*)bvh;
@@ -551,10 +552,10 @@ static int bvh_check(const void* bvh, int n, hipStream_t stream) {
   return CTD_OK;
 }
 
-int render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, const int* faces, int n_faces,
-                             const float* cam_p, int cam_w, int cam_h, const float* proj_p, int proj_w, int proj_h,
-                             const float* shader, const float* pattern, float d_alpha, float d_beta, float* depth,
-                             float* color, float* normal, hipStream_t stream) {
+static int render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, const int* faces,
+                                    int n_faces, const float* cam_p, int cam_w, int cam_h, const float* proj_p,
+                                    int proj_w, int proj_h, const float* shader, const float* pattern, float d_alpha,
+                                    float d_beta, float* depth, float* color, float* normal, hipStream_t stream) {
   const int st = bvh_check(bvh, n_faces, stream);
   if (st != CTD_OK) return st;
   const CamDev cam = make_cam(cam_p, cam_w, cam_h), proj = make_cam(proj_p, proj_w, proj_h);
@@ -565,9 +566,9 @@ int render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* c
   return CTD_OK;
 }
 
-int render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals, const int* faces,
-                        int n_faces, const float* cam_p, int cam_w, int cam_h, const float* shader, float* depth,
-                        float* color, float* normal, hipStream_t stream) {
+static int render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals,
+                               const int* faces, int n_faces, const float* cam_p, int cam_w, int cam_h,
+                               const float* shader, float* depth, float* color, float* normal, hipStream_t stream) {
   const int st = bvh_check(bvh, n_faces, stream);
   if (st != CTD_OK) return st;
   const CamDev cam = make_cam(cam_p, cam_w, cam_h);
@@ -579,3 +580,60 @@ int render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_mesh_bvh_bytes(int n_faces) {
+  return n_faces < 0 || n_faces > kBvhMaxFaces ? 0 : mesh_bvh_bytes(n_faces);
+}
+
+size_t ctd_mesh_bvh_workspace_bytes(int n_faces) {
+  return n_faces < 0 || n_faces > kBvhMaxFaces ? 0 : mesh_bvh_workspace_bytes(n_faces);
+}
+
+int ctd_mesh_bvh_build_f32(const float* verts, int n_verts, const int* faces, int n_faces, void* bvh, size_t bvh_bytes,
+                           void* workspace, size_t workspace_bytes, int* depth, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || !bvh) return CTD_ERR_INVALID_ARG;
+  if (n_faces > 0 && (!verts || !faces || !workspace || n_verts == 0)) return CTD_ERR_INVALID_ARG;
+  if ((uintptr_t)bvh % 16 || (uintptr_t)workspace % 16) return CTD_ERR_INVALID_ARG;
+  if (bvh_bytes < mesh_bvh_bytes(n_faces)) return CTD_ERR_INVALID_ARG;
+  if (workspace_bytes < mesh_bvh_workspace_bytes(n_faces)) return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return mesh_bvh_build_f32(verts, faces, n_faces, bvh, workspace, depth, (hipStream_t)stream);
+}
+
+int ctd_render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, int n_verts, const int* faces,
+                                 int n_faces, const float* cam, int cam_width, int cam_height, const float* proj,
+                                 int proj_width, int proj_height, const float* shader, const float* pattern,
+                                 float d_alpha, float d_beta, float* depth, float* color, float* normal, int device,
+                                 void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || cam_width <= 0 || cam_height <= 0 || proj_width <= 0 ||
+      proj_height <= 0 || (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!bvh || (uintptr_t)bvh % 16 || !cam || !proj || !shader || !pattern || !color ||
+      (n_faces > 0 && (!verts || !colors || !faces)))
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_proj_bvh_f32(bvh, verts, colors, faces, n_faces, cam, cam_width, cam_height, proj, proj_width,
+                                  proj_height, shader, pattern, d_alpha, d_beta, depth, color, normal, (hipStream_t)stream);
+}
+
+int ctd_render_mesh_bvh_f32(const void* bvh, const float* verts, const float* colors, const float* normals, int n_verts,
+                            const int* faces, int n_faces, const float* cam, int cam_width, int cam_height,
+                            const float* shader, float* depth, float* color, float* normal, int device, void* stream) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > kBvhMaxFaces || cam_width <= 0 || cam_height <= 0 ||
+      (double)cam_width * cam_height * 3 >= 2147483648.0)
+    return CTD_ERR_INVALID_ARG;
+  if (!bvh || (uintptr_t)bvh % 16 || !cam || !shader || (n_faces > 0 && (!verts || !faces))) return CTD_ERR_INVALID_ARG;
+  if (n_faces > 0 && ((color && !colors) || ((color || normal) && !normals))) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return render_mesh_bvh_f32(bvh, verts, colors, normals, faces, n_faces, cam, cam_width, cam_height, shader, depth,
+                             color, normal, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -21,7 +21,7 @@
 //
 // Traffic with V = the volume's bytes: the first direction reads C and stores S (2 V), every other one reads C and S
 // and stores S (3 V), the argmin reads S: 12 V for 4 paths, 24 V for 8.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_wave.h"
 
 namespace ctd {
@@ -241,13 +241,13 @@ int launch_sweep(const float* vol, float* S, int frames, int D, int H, int W, in
 
 }  // namespace
 
-bool sgm_supported(int frames, int D, int H, int W) {
+static bool sgm_supported(int frames, int D, int H, int W) {
   // one workgroup per (frame, 32 paths) / (frame, row) on grid.x
   return D <= 256 && (double)frames * ceil_div(W, 32) < 2147483648.0 && (double)frames * H < 2147483648.0;
 }
 
-int sgm_aggregate_f32(const float* vol, bool maximise, float p1, float p2, int paths, float* S, int64_t* idx, float* best,
-                      int frames, int D, int H, int W, hipStream_t stream) {
+static int sgm_aggregate_f32(const float* vol, bool maximise, float p1, float p2, int paths, float* S, int64_t* idx,
+                             float* best, int frames, int D, int H, int W, hipStream_t stream) {
   static const int kDirs[8][2] = {{0, 1}, {0, -1}, {1, 0}, {1, 1}, {1, -1}, {-1, 0}, {-1, 1}, {-1, -1}};   // (dy, dx)
   static const int kFour[4] = {0, 1, 2, 5};
   // 64 paths per workgroup where that fills the card and the D / 8 chunks fit 1024 threads, 32 otherwise
@@ -279,3 +279,35 @@ int sgm_aggregate_f32(const float* vol, bool maximise, float p1, float p2, int p
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool sgm_args_ok(int frames, int D, int H, int W, int paths, float p1, float p2) {
+  if (frames <= 0 || D <= 0 || H <= 0 || W <= 0 || (paths != 4 && paths != 8)) return false;
+  if ((double)frames * D * H * W >= 2147483648.0) return false;
+  return p1 >= 0.f && p2 >= p1 && p2 <= 3.402823466e38f;                                       // (a NaN fails >=)
+}
+
+size_t ctd_sgm_workspace_bytes(int frames, int D, int H, int W, int paths, int want_volume) {
+  if (!sgm_args_ok(frames, D, H, W, paths, 0.f, 0.f) || !sgm_supported(frames, D, H, W) || want_volume) return 0;
+  return sizeof(float) * (size_t)frames * D * H * W;
+}
+
+int ctd_sgm_aggregate_f32(const float* vol, int maximise, float p1, float p2, int paths, float* S_out, int64_t* idx,
+                          float* best, int frames, int D, int H, int W, void* workspace, size_t workspace_bytes,
+                          int device, void* stream) {
+  if (!sgm_args_ok(frames, D, H, W, paths, p1, p2)) return CTD_ERR_INVALID_ARG;
+  if (!vol || !idx || !best) return CTD_ERR_INVALID_ARG;
+  if (!sgm_supported(frames, D, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!S_out && (!workspace || workspace_bytes < ctd_sgm_workspace_bytes(frames, D, H, W, paths, 0) ||
+                 ((uintptr_t)workspace & 15)))
+    return CTD_ERR_WORKSPACE;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return sgm_aggregate_f32(vol, maximise != 0, p1, p2, paths, S_out ? S_out : (float*)workspace, idx, best, frames, D, H, W,
+                           (hipStream_t)stream);
+}
+
+}  // extern "C"

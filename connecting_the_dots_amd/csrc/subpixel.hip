@@ -15,9 +15,10 @@
 // Costs.  costvol_ref_cost (ctd_costvol_ref.h) is the tap loop of ctd_costvol_f32; subpixel_cost3 below walks the taps
 // once for the three disparities, with the image-side soft step of the census types (independent of d) computed once
 // per tap.  Every cost keeps its own chain and its own per-term operations, so the bits are those of ctd_costvol_f32.
+#include "ctd_common.h"
 #include "ctd_costvol_ref.h"
-#include "ctd_internal.h"
 #include "ctd_ncc_point.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 
@@ -78,7 +79,7 @@ static SubpixelLayout subpixel_layout(int frames, int H, int W, int D, bool per_
   return l;
 }
 
-size_t xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern) {
+static size_t xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern) {
   if (frames <= 0) return 0;
   return subpixel_layout(frames, H, W, D, per_frame_pattern).bytes;
 }
@@ -200,9 +201,9 @@ __global__ __launch_bounds__(256) void xcorrvol_subpixel_kernel(const float* __r
   if (refined) refined[p] = ok ? 1 : 0;
 }
 
-int xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx, float* disp,
-                          uint8_t* refined, int frames, int H, int W, int D, int bs, int mode, bool prepared,
-                          void* workspace, hipStream_t stream) {
+static int xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                                 float* disp, uint8_t* refined, int frames, int H, int W, int D, int bs, int mode,
+                                 bool prepared, void* workspace, hipStream_t stream) {
   const bool per_frame = in1_frame_stride != 0;
   const SubpixelLayout l = subpixel_layout(frames, H, W, D, per_frame);
   char* ws = (char*)workspace;
@@ -333,9 +334,9 @@ __global__ __launch_bounds__(256) void costvol_subpixel_kernel(const float* __re
   if (refined) refined[p] = ok ? 1 : 0;
 }
 
-int costvol_subpixel_f32(const float* im, const float* pat, long pat_frame_stride, const int64_t* idx, float* disp,
-                         uint8_t* refined, int frames, int H, int W, int D, int bs, int type, float eps, int mode,
-                         hipStream_t stream) {
+static int costvol_subpixel_f32(const float* im, const float* pat, long pat_frame_stride, const int64_t* idx,
+                                float* disp, uint8_t* refined, int frames, int H, int W, int D, int bs, int type,
+                                float eps, int mode, hipStream_t stream) {
   const long n = (long)frames * H * W;
   const dim3 g((unsigned)((n + 255) / 256));
   switch (type) {
@@ -349,3 +350,49 @@ int costvol_subpixel_f32(const float* im, const float* pat, long pat_frame_strid
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+size_t ctd_xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, int block_size, int per_frame_pattern) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0) return 0;
+  return xcorrvol_subpixel_workspace_bytes(frames, H, W, D, per_frame_pattern != 0);
+}
+
+int ctd_xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_frame_stride, const int64_t* idx,
+                              float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int mode,
+                              void* workspace, size_t workspace_bytes, int device, void* stream) {
+  const bool prepared = (mode & CTD_PATTERN_PREPARED) != 0;
+  mode &= ~CTD_PATTERN_PREPARED;
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0 ||
+      (mode != CTD_SUBPIXEL_PARABOLA && mode != CTD_SUBPIXEL_EQUIANGULAR))
+    return CTD_ERR_INVALID_ARG;
+  if (in1_frame_stride != 0 && in1_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!in0 || !in1 || !idx || !disp) return CTD_ERR_INVALID_ARG;
+  if (!workspace || ((uintptr_t)workspace & 255) ||
+      workspace_bytes < xcorrvol_subpixel_workspace_bytes(frames, H, W, D, in1_frame_stride != 0))
+    return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return xcorrvol_subpixel_f32(in0, in1, in1_frame_stride, idx, disp, refined, frames, H, W, D, block_size, mode,
+                               prepared, workspace, (hipStream_t)stream);
+}
+
+int ctd_costvol_subpixel_f32(const float* im, const float* pattern, long pattern_frame_stride, const int64_t* idx,
+                             float* disp, uint8_t* refined, int frames, int H, int W, int D, int block_size, int type,
+                             float eps, int mode, int device, void* stream) {
+  if (!vol_shape_ok(frames, 1, H, W, D, block_size) || (block_size & 1) == 0 || type < 0 || type > 3 ||
+      (mode != CTD_SUBPIXEL_PARABOLA && mode != CTD_SUBPIXEL_EQUIANGULAR))
+    return CTD_ERR_INVALID_ARG;
+  if (pattern_frame_stride != 0 && pattern_frame_stride != (long)H * W) return CTD_ERR_INVALID_ARG;
+  if (frames == 0) return CTD_OK;
+  if (!im || !pattern || !idx || !disp) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return costvol_subpixel_f32(im, pattern, pattern_frame_stride, idx, disp, refined, frames, H, W, D, block_size, type,
+                              eps, mode, (hipStream_t)stream);
+}
+
+}  // extern "C"

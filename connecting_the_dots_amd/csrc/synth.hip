@@ -6,7 +6,7 @@
 // The operation orders these kernels keep, and what they assume of OpenCV, are stated with the entry points in
 // include/ctd_hip.h (ctd_syn_finish_f32, ctd_augment_f32, ctd_salt_pepper_f32).  Nothing here uses an FMA: the
 // library builds with -ffp-contract=off.
-#include "ctd_internal.h"
+#include "ctd_common.h"
 #include "ctd_lcn_window.h"
 
 namespace ctd {
@@ -107,9 +107,9 @@ __global__ __launch_bounds__(256) void syn_finish_kernel(const float* __restrict
   }
 }
 
-int syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend, double bf,
-                   float thr, int ks, float eps, int clip, float* im, float* amb, float* grad, float* disp, float* mask,
-                   int N, int H, int W, hipStream_t stream) {
+static int syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend, double bf,
+                          float thr, int ks, float eps, int clip, float* im, float* amb, float* grad, float* disp,
+                          float* mask, int N, int H, int W, hipStream_t stream) {
   const int R = ks + 2;
   const size_t lds = sizeof(float) * ((size_t)(kFinTW + 2 * R) * (kFinTH + 2 * R) +
                                       2 * (size_t)(kFinTH + 2 * R) * (kFinTW + 2 * ks) +
@@ -207,8 +207,8 @@ __global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ 
   }
 }
 
-int augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
-                uint32_t* minmax, int N, int H, int W, hipStream_t stream) {
+static int augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
+                       uint32_t* minmax, int N, int H, int W, hipStream_t stream) {
   CTD_HIP_TRY(hipMemsetAsync(minmax, 0, sizeof(uint32_t) * 2 * (size_t)N, stream));
   dim3 grid(ceil_div(W, kAugTW), ceil_div(H, kAugTH), N);
   hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, stream, img, noise, noise_f64, params, out, minmax, H, W);
@@ -242,8 +242,8 @@ __global__ __launch_bounds__(256) void salt_pepper_kernel(float* __restrict__ im
   }
 }
 
-int salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
-                    const int64_t* pepper, int kmax, int N, int H, int W, hipStream_t stream) {
+static int salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
+                           const int64_t* pepper, int kmax, int N, int H, int W, hipStream_t stream) {
   if (kmax == 0) return CTD_OK;
   hipLaunchKernelGGL(salt_pepper_kernel, dim3(N), dim3(256), 0, stream, img, minmax, counts, salt, pepper, kmax,
                      (long)H * W);
@@ -252,3 +252,46 @@ int salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, c
 }
 
 }  // namespace ctd
+
+using namespace ctd;
+
+extern "C" {
+
+static bool syn_shape_ok(int N, int H, int W) {
+  return N >= 0 && N <= 65535 && H > 0 && W > 0 && (double)H * W * 3 < 2147483648.0;
+}
+
+int ctd_syn_finish_f32(const float* depth, const float* color, const float* normal, const double* blend,
+                       double baseline_focal, float grad_threshold, int lcn_radius, float lcn_eps, int lcn_clip,
+                       float* im, float* ambient, float* grad, float* disp, float* mask, int N, int H, int W, int device,
+                       void* stream) {
+  if (!syn_shape_ok(N, H, W) || lcn_radius < 0) return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!depth || !color || !normal || !blend || !im || !ambient || !grad) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return syn_finish_f32(depth, color, normal, blend, baseline_focal, grad_threshold, lcn_radius, lcn_eps, lcn_clip, im,
+                        ambient, grad, disp, mask, N, H, W, (hipStream_t)stream);
+}
+
+int ctd_augment_f32(const float* img, const void* noise, int noise_f64, const ctd_augment_params* params, float* out,
+                    uint32_t* minmax, int N, int H, int W, int device, void* stream) {
+  if (!syn_shape_ok(N, H, W) || (noise_f64 != 0 && noise_f64 != 1)) return CTD_ERR_INVALID_ARG;
+  if (N == 0) return CTD_OK;
+  if (!img || !params || !out || !minmax) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return augment_f32(img, noise, noise_f64, params, out, minmax, N, H, W, (hipStream_t)stream);
+}
+
+int ctd_salt_pepper_f32(float* img, const uint32_t* minmax, const int32_t* counts, const int64_t* salt,
+                        const int64_t* pepper, int kmax, int N, int H, int W, int device, void* stream) {
+  if (!syn_shape_ok(N, H, W) || kmax < 0) return CTD_ERR_INVALID_ARG;
+  if (N == 0 || kmax == 0) return CTD_OK;
+  if (!img || !minmax || !counts || !salt || !pepper) return CTD_ERR_INVALID_ARG;
+  DeviceGuard g(device);
+  if (g.status) return g.status;
+  return salt_pepper_f32(img, minmax, counts, salt, pepper, kmax, N, H, W, (hipStream_t)stream);
+}
+
+}  // extern "C"
