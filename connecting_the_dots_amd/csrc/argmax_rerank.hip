@@ -123,7 +123,7 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
                                              const float* __restrict__ in1, long in1_frame_stride,
                                              int64_t* __restrict__ idx, float* __restrict__ best, int D, int H, int W, int bs,
                                              float eps, WorkList work, RunSource rsrc, unsigned role_block,
-                                             unsigned n_role_blocks, unsigned waves_used = 4) {
+                                             unsigned n_role_blocks, unsigned waves_used = 4, unsigned* stamp = nullptr) {
   // `waves_used` of the workgroup's four wavefronts work (the tail kernel uses two: half the staging LDS per workgroup,
   // so that seven workgroups fit a CU instead of three and the other roles of that launch keep their concurrency)
   if ((threadIdx.x >> 6) >= waves_used) return;
@@ -151,6 +151,7 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
     longest = max(longest, seg_cnt[k]);
   }
   const unsigned n_slots = longest * (unsigned)work.parts;
+  CTD_POST_STAMP_S(stamp, 1, longest);                         // counters read
   const unsigned n_waves = n_role_blocks * waves_used;
   for (unsigned slot = role_block * waves_used + (threadIdx.x >> 6); slot < n_slots; slot += n_waves) {
     const unsigned seg = slot & (unsigned)(work.parts - 1), entry = slot / (unsigned)work.parts;
@@ -159,6 +160,8 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
     for (int k = 0; k < kWorkListParts; ++k) cnt = seg == (unsigned)k ? seg_cnt[k] : cnt;
     if (entry >= cnt) continue;                            // wave-uniform: this segment is shorter
     const long pj = work.list[(long)seg * work.seg_cap + entry];   // wave-uniform from here on
+    CTD_POST_STAMP_S(stamp, 2, pj);                            // list entry read
+    CTD_POST_STAMP_ITEM(stamp);
     const long fj = pj / HW, qj = pj - fj * HW;
     const int hj = (int)(qj / W), wj = (int)(qj - (long)hj * W);
     const float* v = VOL ? vol + fj * D * HW + qj : nullptr;
@@ -181,6 +184,7 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
         x[wd] = v[(long)(rsrc.run_vals ? min(d, d_clamped) : d) * HW];
         if (run_listed && d >= d_clamped) x[wd] = rv;
       }
+      CTD_POST_STAMP_V(stamp, 3, x[0]);                        // column read
     }
     // !VOL (every pixel of the list is re-scored): the frame window and the pattern rows are requested at once, one
     // batch of independent loads per lane held in registers (block 9, D <= 128: kPreA + kPreB of them; -5 us of 0.53 ms).
@@ -278,6 +282,7 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
           }
       }
     }
+    CTD_POST_STAMP(stamp, 4);                                  // rows staged (or no re-scoring needed)
     // Exact re-scoring, lane <-> candidate (ascending d): every lane runs the reference's serial accumulations for
     // its own candidate out of LDS (a whole-wave evaluation of one candidate at a time, fed by v_readlane, costs
     // ~15 us per candidate; this costs ~3 us for all of them).  Then the lowest d among the best exact scores.
@@ -309,6 +314,7 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
       for (int wd = 0; wd < WORDS; ++wd)
         if (mask[wd]) ei = min(ei, wd * 64 + __ffsll((long long)mask[wd]) - 1);
     }
+    CTD_POST_STAMP_S(stamp, 5, ei);                            // re-scored
     if (lane == 0) {
       idx[pj] = ei;
       if (best) {
@@ -316,6 +322,9 @@ __device__ __forceinline__ void resolve_role(float* lds_resolve, const float* __
         else if (rescore) best[pj] = eb;                     // no fast score exists: the reference-order one
       }
     }
+    CTD_POST_STAMP(stamp, 6);                                  // written
+    CTD_POST_STAMP(stamp, 9);                                  // exit of the wavefront's first item
+    stamp = nullptr;
   }
 }
 
@@ -365,19 +374,22 @@ __global__ __launch_bounds__(256) void rank_tail_kernel(float* __restrict__ vol,
   // (nobody reads slot 0 in this launch -- the decode role takes the count from slot 3, ncc_fixup_kernel -- and the next
   // call's pre-pass counts its listed frame windows from zero in it)
   if (blockIdx.x == 0 && threadIdx.x == 0) counters[0] = 0u;
+  unsigned* stamp = CTD_POST_STAMP_SLOT(role);                  // entry
   if (role == 0) {
     resolve_role<WORDS, VOL>(lds_dyn, vol, in0, in1, in1_frame_stride, idx, best, D, H, W, bs, eps, work, rsrc, rb, n_resolve,
-                             kTailResolveWaves);
+                             kTailResolveWaves, stamp);
   } else if (role == 1) {
     if constexpr (VOL)
       runs_role(vol, rsrc.run_vals, counters, run_rows, rsrc.per_frame, 1, H, W, D, bs, (int)(rb >> 2), (int)(rb & 3), 4,
-                (int*)lds_dyn);
+                (int*)lds_dyn, stamp);
   } else {
     decode_role((unsigned long long*)idx, best, flags, counters, flag_a, flag_b, rsrc.per_frame, frames, H, W, D,
-                rb * 4 + (threadIdx.x >> 6), n_decode * 4);
+                rb * 4 + (threadIdx.x >> 6), n_decode * 4, stamp);
   }
 }
 
+
+CTD_POST_STAMP_EXPORT(ctd_debug_read_tail_stamps)
 
 template <bool VOL>
 static int launch_resolve(const float* vol, const float* in0, const float* in1, long in1_frame_stride, int64_t* idx,

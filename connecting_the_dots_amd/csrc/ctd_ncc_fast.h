@@ -33,6 +33,22 @@ inline PlaneGeometry plane_geometry(int W, int D) {
   return g;
 }
 
+// Pattern-side table of the fix-up pass (ncc_fixup.hip): per listed pattern window the 81 centred taps and the sum of
+// their squares, padded to a multiple of 4 floats; block 9, single channel, the first kFixTabCap listed windows (1.3 MB).
+// The table takes no workspace of its own (the sizes the workspace queries answer are part of the ABI): it lives in the
+// unused END of the pattern's window list.  That list has room for every window of the pattern planes (H x W1 per image)
+// and even an all-constant pattern lists H x (W + 4) of them, so row j sits at the buffer's end minus (j + 1) rows, and
+// the rows that fit behind the n_b entries actually listed -- fixup_table_rows, evaluated on the device by the kernel
+// that fills the table and by the one that reads it -- are the table; windows past them are staged in the kernel.
+constexpr int kFixTabCap = 4096, kFixTabRow = 84;
+inline bool fixup_table_covers(int C, int bs) { return C == 1 && bs == 9; }
+__host__ __device__ inline unsigned fixup_table_rows(unsigned n_b, unsigned list_cap) {
+  const unsigned used = n_b < list_cap ? n_b : list_cap;
+  const unsigned long long room = (unsigned long long)(list_cap - used) * sizeof(unsigned long long) / (kFixTabRow * sizeof(float));
+  const unsigned want = used < (unsigned)kFixTabCap ? used : (unsigned)kFixTabCap;
+  return room < want ? (unsigned)room : want;
+}
+
 struct FastWorkspace {
   float *ac, *m0, *v0;        // centred frames, their window mean (centred) / deviation planes   [N*C][H][W]
   float *bc, *m1, *v1;        // same for the pattern, per UNCLAMPED window-centre column          [..][H][W1]
@@ -42,6 +58,11 @@ struct FastWorkspace {
   unsigned long long *flag_a, *flag_b;
   unsigned long long* run_rows;   // (pattern image << 20 | h) of the listed fully clamped pattern windows
   float* run_vals;            // [frames][H][D] exact values of the fully clamped runs (ncc_fixup_runs_kernel)
+  unsigned flag_b_cap;        // entries flag_b has room for
+  float* fix_tab_end;         // end of flag_b's buffer: row j of the fix-up's pattern-side table (ncc_fixup.hip) is the
+                              // kFixTabRow floats at fix_tab_end - (j + 1) * kFixTabRow, in flag_b order; filled when the
+                              // pattern is prepared and, like counters[1..2], flag_b and run_rows, the pattern's: no
+                              // per-call kernel writes it
   size_t bytes;               // end of the volume pass's own workspace; the ranking buffers (RankPlan) follow
 };
 
@@ -82,10 +103,14 @@ struct PrepassJob {
 int launch_prepass(const PrepassJob& ja, const PrepassJob& jb, int H, int W, int bs, const WorkList* work,
                    hipStream_t stream);
 
-// ncc_fixup.hip: fix-up of the listed windows (+ the run spreading of an unranked call)
+// ncc_fixup.hip: fix-up of the listed windows (+ the run spreading of an unranked call).  `tab`: the pattern-side table
+// of a prepared pattern (ws.fix_tab_end), or null: the pattern side is staged in the kernel.
 int launch_fixup(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames, int C, int H, int W,
-                 int D, int bs, const FastWorkspace& ws, bool per_frame, const RankPlan* rank, const float* best,
-                 unsigned* scan_counter, hipStream_t stream);
+                 int D, int bs, const FastWorkspace& ws, bool per_frame, const float* tab, const RankPlan* rank,
+                 const float* best, unsigned* scan_counter, hipStream_t stream);
+// the table itself, behind the pattern's pre-pass (ncc_fast_prepare_pattern_f32)
+int launch_fixup_table(const float* in1, long in1_frame_stride, int C, int H, int W, int bs, const FastWorkspace& ws,
+                       hipStream_t stream);
 
 // ncc_tiles.hip: the volume by disparity groups, one accumulating launch per channel; bs in {3, 5, 7, 9}.  Block 9 with
 // W % 4 == 0 and an aligned volume goes to the tile-256 kernel (ncc_t256.hip), every other shape to the wide + narrow pair.

@@ -1,6 +1,7 @@
 // ctd_tail.h -- device roles shared by the tail passes of the fast NCC path (ncc_fixup.hip, argmax_rerank.hip).
 #pragma once
 #include "ctd_common.h"
+#include "ctd_post_stamps.h"
 
 namespace ctd {
 
@@ -30,7 +31,8 @@ constexpr int kRunPlanes = 8;
 
 __device__ inline void runs_role(float* __restrict__ out, const float* __restrict__ run_vals,
                                  const unsigned* __restrict__ counters, const unsigned long long* __restrict__ run_rows,
-                                 int per_frame, int C, int H, int W, int D, int bs, int bx, int by, int gy, int* s_rows) {
+                                 int per_frame, int C, int H, int W, int D, int bs, int bx, int by, int gy, int* s_rows,
+                                 unsigned* stamp = nullptr) {
   __shared__ int s_n;
   const int tid = threadIdx.x;
   // a workgroup serves kRunPlanes consecutive disparity planes of one frame: the list scan and the loads of the run
@@ -42,6 +44,7 @@ __device__ inline void runs_role(float* __restrict__ out, const float* __restric
   const int tail = bs - 1 - bs / 2;
   const int seg_max = min(d1 - tail + 1, W);               // plane d: pixels w in [0, d - tail]
   const unsigned n_r = counters[2];
+  CTD_POST_STAMP_S(stamp, 1, n_r);                             // counters read
   if (seg_max <= 0 || n_r == 0) return;                    // (workgroup-uniform)
   if (tid == 0) s_n = 0;
   __syncthreads();
@@ -52,6 +55,8 @@ __device__ inline void runs_role(float* __restrict__ out, const float* __restric
     if ((!per_frame || z / C == f) && h % gy == by) s_rows[atomicAdd(&s_n, 1)] = h;
   }
   __syncthreads();
+  CTD_POST_STAMP(stamp, 2);                                    // this share's rows listed
+  if (s_n > 0) CTD_POST_STAMP_ITEM(stamp);
   const long HW = (long)H * W;
   // 32 lanes x 4 pixels span 128 pixels of a row, 8 rows per sweep of the workgroup: no index divisions, 16-byte
   // accesses wherever the quad lies inside the run and the row starts are 16-byte aligned
@@ -95,6 +100,8 @@ __device__ inline void runs_role(float* __restrict__ out, const float* __restric
       }
     }
   }
+  CTD_POST_STAMP(stamp, 6);                                    // written
+  CTD_POST_STAMP(stamp, 9);
 }
 
 // Patched index words -> plain indices and best scores.  One wavefront per (listed pattern window, frame), lane <->
@@ -104,7 +111,7 @@ __device__ inline void decode_role(unsigned long long* __restrict__ idx, float* 
                                    const unsigned char* __restrict__ flags, const unsigned* __restrict__ counters,
                                    const unsigned long long* __restrict__ list_a,
                                    const unsigned long long* __restrict__ list_b, int per_frame, int frames, int H, int W,
-                                   int D, unsigned wave, unsigned n_waves) {
+                                   int D, unsigned wave, unsigned n_waves, unsigned* stamp = nullptr) {
   const int lane = threadIdx.x & 63;
   // listed FRAME windows: every score of their pixel was a placeholder, so the pixel is normally on the work list
   // (all its keys tie); a pixel with a single score (D = 1, or w = 0 of a one-disparity run) is not -- decode it here
@@ -119,12 +126,15 @@ __device__ inline void decode_role(unsigned long long* __restrict__ idx, float* 
     }
   }
   const unsigned n_b = counters[1];
+  CTD_POST_STAMP_S(stamp, 1, n_b);                             // counters read (the frame windows are done)
   const unsigned per_b = per_frame ? 1u : (unsigned)frames;
   for (unsigned item = wave; item < n_b * per_b; item += n_waves) {
     const unsigned jb = item / per_b;
     const unsigned long long e = list_b[jb];
     const int z = (int)(e >> 40), h = (int)((e >> 20) & 0xFFFFF), col = (int)(e & 0xFFFFF) - 0x80000;
     const int f = per_frame ? z : (int)(item - jb * per_b);          // (ranked calls are single channel: z = frame)
+    CTD_POST_STAMP_S(stamp, 2, col);                           // list entry read
+    CTD_POST_STAMP_ITEM(stamp);
     for (int d = lane; d < D; d += 64) {
       const int w = col + d;
       if (w < 0 || w >= W) continue;
@@ -135,6 +145,9 @@ __device__ inline void decode_role(unsigned long long* __restrict__ idx, float* 
         best[pix] = f32_unordered((unsigned)(k >> 32));
       }
     }
+    CTD_POST_STAMP(stamp, 6);                                  // written
+    CTD_POST_STAMP(stamp, 9);                                  // exit of the wavefront's first item
+    stamp = nullptr;
   }
 }
 

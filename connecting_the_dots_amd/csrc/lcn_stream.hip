@@ -33,6 +33,7 @@
 #include <cstdlib>
 
 #include "ctd_common.h"
+#include "ctd_internal.h"
 #include "ctd_prepass.h"
 #include "ctd_wave.h"
 
@@ -432,9 +433,7 @@ int lcn_stream_f32(const float* x, float* y, float* stds, int N, int H, int W, f
   // one workgroup (three wavefronts) per (strip, band, frame); every band pays 18 warm-up rows, and four workgroups per
   // CU are resident side by side on its four SIMDs: as many bands as give at most 4 x CUs workgroups (A/B at config 2,
   // rocprofv3, f32 sums: 768 workgroups 33.9 us, 864 32.5, 960 / 1008 31.4, 1152 38.0, 1280 38.2)
-  int target = 1024, dev = 0, n_cu = 0;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0)
-    target = 4 * n_cu;
+  int target = 4 * device_cu_count();                          // (asked once per device, ncc_alld.hip)
 #ifdef CTD_LS_KNOBS   // (variant builds only: the workgroup-count sweep of tools/r5_prof_fused.sh)
   if (const char* e = getenv("CTD_LS_WAVES")) target = atoi(e);
 #endif

@@ -13,7 +13,13 @@
 //     4. argmax_rerank.hip tail kernel: runs, decode, exact re-scoring of the work list (rank_tail_f32, the caller's)
 //   fused call (ctd_lcn_xcorrvol_argmax_f32): a ranked call whose stage 1 is lcn_stream.hip for the frames (LCN and
 //     their planes in one launch) and ncc_prepass.hip for the pattern alone, unless the pattern was prepared
-//   prepared pattern (ncc_fast_prepare_pattern_f32): the pattern half of stage 1, once; later calls skip it.
+//   prepared pattern (ncc_fast_prepare_pattern_f32): the pattern half of stage 1, once; later calls skip it.  Block 9,
+//     single channel: a small launch behind it (ncc_fixup_table_kernel) fills the table at FastWorkspace::fix_tab_end (the unused end of flag_b), the pattern side of
+//     the fix-up items (centred taps and their sum of squares per listed pattern window, in flag_b order, the first
+//     kFixTabCap of them or as many as fit there).  The table is the pattern's, like counters[1..2], flag_b and run_rows: no per-call kernel
+//     writes it.  Calls on the prepared pattern hand it to the fix-up, which then runs one item per (listed pattern
+//     window, frame, block of 64 disparities) -- ncc_fixup_items_kernel; unprepared calls pass null and launch the
+//     table-less kernel.
 // Shared declarations: ctd_ncc_fast.h.  Same op as ncc_exact.hip, to |a-b| <= 1e-5*|b| + 1e-6 (ncc_tiles.hip, ncc_fixup.hip).
 #include "ctd_ncc_fast.h"
 #include "ctd_prepass.h"
@@ -54,6 +60,8 @@ static FastWorkspace fast_workspace(void* base, int frames, int C, int H, int W,
   // flag lists: room for every frame window and every pattern window the outputs can touch
   ws.flag_a = (unsigned long long*)take(img0 * W * sizeof(unsigned long long));
   ws.flag_b = (unsigned long long*)take(img1 * ws.W1 * sizeof(unsigned long long));
+  ws.flag_b_cap = (unsigned)(img1 * ws.W1);
+  ws.fix_tab_end = (float*)(ws.flag_b + ws.flag_b_cap);        // the fix-up's table grows down from the list's end (ctd_ncc_fast.h)
   ws.run_rows = (unsigned long long*)take(img1 * sizeof(unsigned long long));
   ws.run_vals = (float*)take((size_t)frames * H * D * sizeof(float));
   ws.bytes = off;
@@ -141,7 +149,9 @@ static int ncc_fast_prepare_pattern_f32(const float* in1, long in1_frame_stride,
   if (workspace == nullptr || workspace_bytes < ws.bytes) return CTD_ERR_WORKSPACE;
   CTD_HIP_TRY(hipMemsetAsync(ws.counters, 0, 16, stream));
   const PrepassJobs j = prepass_jobs(ws, in1, in1, C, H, W, bs, 0, (per_frame ? frames : 1) * C);   // (no frame images in this launch)
-  return launch_prepass(j.frames, j.pattern, H, W, bs, nullptr, stream);
+  const int st = launch_prepass(j.frames, j.pattern, H, W, bs, nullptr, stream);
+  if (st) return st;
+  return launch_fixup_table(in1, in1_frame_stride, C, H, W, bs, ws, stream);   // the fix-up's pattern side, once (ncc_fixup.hip)
 }
 
 // The volume stage.  Block 9, W % 4 == 0, one channel, aligned volume: the all-D kernel, with the ranking (`rank`) or
@@ -214,8 +224,8 @@ static int ncc_fast_f32(const float* in0, const float* in1, long in1_frame_strid
   if (st) return st;
   st = launch_volume(out, frames, C, H, W, D, bs, ws, per_frame, rank, stream);
   if (st || rank) return st;
-  st = launch_fixup(in0, in1, in1_frame_stride, out, frames, C, H, W, D, bs, ws, per_frame, nullptr, nullptr,
-                    (unsigned*)workspace, stream);
+  st = launch_fixup(in0, in1, in1_frame_stride, out, frames, C, H, W, D, bs, ws, per_frame,
+                    pattern_prepared ? ws.fix_tab_end : nullptr, nullptr, nullptr, (unsigned*)workspace, stream);
   if (st == CTD_OK && pattern_prepared) CTD_HIP_TRY(hipMemsetAsync(ws.counters, 0, 4, stream));   // (see above: [0] stays zero between calls)
   return st;
 }
@@ -224,10 +234,11 @@ static int ncc_fast_f32(const float* in0, const float* in1, long in1_frame_strid
 // run values) with every recomputed score held against the `best` / `idx` of its pixel.
 static int ncc_fast_fixup_ranked(const float* in0, const float* in1, long in1_frame_stride, float* out, int frames,
                                  int H, int W, int D, int bs, void* workspace, const RankPlan& rank, const float* best,
-                                 hipStream_t stream) {
+                                 bool pattern_prepared, hipStream_t stream) {
   const bool per_frame = in1_frame_stride != 0;
   FastWorkspace ws = fast_workspace(workspace, frames, 1, H, W, D, per_frame);
-  return launch_fixup(in0, in1, in1_frame_stride, out, frames, 1, H, W, D, bs, ws, per_frame, &rank, best, nullptr, stream);
+  return launch_fixup(in0, in1, in1_frame_stride, out, frames, 1, H, W, D, bs, ws, per_frame,
+                      pattern_prepared ? ws.fix_tab_end : nullptr, &rank, best, nullptr, stream);
 }
 
 }  // namespace ctd
@@ -324,7 +335,7 @@ int ctd_xcorrvol_argmax_f32(const float* in0, const float* in1, long in1_frame_s
       int st = ncc_fast_f32(in0, in1, in1_frame_stride, vol_out, frames, 1, H, W, D, block_size, workspace,
                             workspace_bytes, &rp, prepared, hs);       // pre-pass + all-D kernel
       if (st) return st;
-      st = ncc_fast_fixup_ranked(in0, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, hs);
+      st = ncc_fast_fixup_ranked(in0, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, prepared, hs);
       if (st) return st;
       return rank_tail_f32(rp, vol_out, in0, in1, in1_frame_stride, idx, rp.best, frames, D, H, W, block_size, hs);
     }
@@ -366,7 +377,7 @@ int ctd_lcn_xcorrvol_argmax_f32(const float* raw, float* lcn_out, float* std_out
   int st = ncc_fast_f32(lcn_out, in1, in1_frame_stride, vol_out, frames, 1, H, W, D, block_size, workspace, workspace_bytes,
                         &rp, prepared, hs, &fused);           // streaming LCN + statistics, then the all-D kernel
   if (st) return st;
-  st = ncc_fast_fixup_ranked(lcn_out, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, hs);
+  st = ncc_fast_fixup_ranked(lcn_out, in1, in1_frame_stride, vol_out, frames, H, W, D, block_size, workspace, rp, rp.best, prepared, hs);
   if (st) return st;
   return rank_tail_f32(rp, vol_out, lcn_out, in1, in1_frame_stride, idx, rp.best, frames, D, H, W, block_size, hs);
 }

@@ -78,7 +78,9 @@ int ctd_xcorrvol_f32(const float* in0, const float* in1, long in1_frame_stride, 
 
 /* Pattern half of the fast path's pre-pass, ONCE per pattern: the reference prepares the pattern once per run
  * (model/exp_synph.py:64-71: LCN of the pattern in the Worker's constructor), its xcorrvol op re-reads it on every call.
- * Writes the pattern's window statistics, its list of windows for the fix-up pass and run rows into `workspace`
+ * Writes the pattern's window statistics, its list of windows for the fix-up pass, its run rows and (block 9, C = 1) the
+ * pattern-side tables of the fix-up pass -- per listed pattern window the centred taps and the sum of their squares, up
+ * to 4096 windows, in the unused end of that list's buffer (the workspace sizes are unchanged) -- into `workspace`
  * (ctd_xcorrvol_argmax_workspace_bytes() for the same frames / shape: the layout depends on all of them).  Afterwards
  * ctd_xcorrvol_f32 / ctd_xcorrvol_argmax_f32 calls with algo = CTD_NCC_FAST | CTD_PATTERN_PREPARED, the SAME workspace,
  * in1, in1_frame_stride, frames and shape skip that half.  The caller keeps the workspace to these calls in between. */
