@@ -1,4 +1,4 @@
-"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h).
+"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h and ctd_hip_band.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -145,6 +145,15 @@ BENCH_SIGNATURES = {
     "ctd_kernel_timing_collect": (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_int)]),
 }
 
+# band-limited matching of include/ctd_hip_band.h (an addition beside ctd_hip.h; torchext.xcorrvol_argmax_band, ...)
+BAND_SIGNATURES = {
+    "ctd_xcorrvol_argmax_band_workspace_bytes": (_c_size_t, [_c_int] * 6),
+    "ctd_xcorrvol_argmax_band_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_vp, _c_size_t,
+                                                                                                  _c_int, _vp]),
+    "ctd_costvol_argmin_band_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float, _c_int,
+                                                                                                 _vp]),
+}
+
 _lib = None
 
 
@@ -157,7 +166,7 @@ def lib():
                 "connecting_the_dots_amd: %s is missing -- build it with "
                 "`python -m connecting_the_dots_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

@@ -12,12 +12,15 @@
 // What remains per pixel is three `dot` chains over the same frame taps; the pattern taps of d+1, d, d-1 are columns
 // j, j+1, j+2 of one row of bs + 2 samples.
 //
+// The workspace layout and the kernels of the first two items: ctd_subpixel_ws.h (shared with band_match.hip).
+//
 // Costs.  costvol_ref_cost (ctd_costvol_ref.h) is the tap loop of ctd_costvol_f32; subpixel_cost3 below walks the taps
 // once for the three disparities, with the image-side soft step of the census types (independent of d) computed once
 // per tap.  Every cost keeps its own chain and its own per-term operations, so the bits are those of ctd_costvol_f32.
 #include "ctd_common.h"
 #include "ctd_costvol_ref.h"
 #include "ctd_ncc_point.h"
+#include "ctd_subpixel_ws.h"
 #include "ctd_validate.h"
 
 namespace ctd {
@@ -59,69 +62,6 @@ __device__ inline float subpixel_fit(float sm, float s0, float sp, bool maximum,
   if (!r) return (float)d;
   delta = delta < -0.5f ? -0.5f : (delta > 0.5f ? 0.5f : delta);   // (a NaN passes, as torch.clamp lets it)
   return (float)d + delta;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// workspace of the NCC refinement
-// ---------------------------------------------------------------------------------------------------------------------
-struct SubpixelLayout {
-  size_t q0, q1, pstat, bytes;
-};
-
-static SubpixelLayout subpixel_layout(int frames, int H, int W, int D, bool per_frame_pattern) {
-  const size_t HW = (size_t)H * W;
-  const size_t P = per_frame_pattern ? (size_t)frames : 1;
-  SubpixelLayout l;
-  l.q0 = 0;                                                     // f32 [frames][H][W]: in0 / bs^2
-  l.q1 = align_up(l.q0 + 4 * (size_t)frames * HW, 256);         // f32 [P][H][W]: in1 / bs^2
-  l.pstat = align_up(l.q1 + 4 * P * HW, 256);                   // float2 [P][H][W + D - 1]: (mu1, s1) at x = col - (D-1)
-  l.bytes = align_up(l.pstat + 8 * P * (size_t)H * (W + D - 1), 256);
-  return l;
-}
-
-static size_t xcorrvol_subpixel_workspace_bytes(int frames, int H, int W, int D, bool per_frame_pattern) {
-  if (frames <= 0) return 0;
-  return subpixel_layout(frames, H, W, D, per_frame_pattern).bytes;
-}
-
-__global__ __launch_bounds__(256) void subpixel_quotient_kernel(const float* __restrict__ x, float* __restrict__ q,
-                                                                long n, float bs2) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) q[i] = x[i] / bs2;
-}
-
-// (mu1, s1) of the pattern window centred at (h, x), x = xo - (D-1), unclamped; the columns clamp tap by tap
-template <int BS>
-__global__ __launch_bounds__(256) void subpixel_pattern_stats_kernel(const float* __restrict__ in1,
-                                                                     const float* __restrict__ q1,
-                                                                     float2* __restrict__ pstat, int P, int H, int W,
-                                                                     int D, int bs_rt) {
-  const int bs = BS ? BS : bs_rt;
-  const int half = bs / 2;
-  const long Wo = (long)W + D - 1;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)P * H * Wo) return;
-  const long ph = i / Wo;
-  const int x = (int)(i - ph * Wo) - (D - 1);
-  const int p = (int)(ph / H), h = (int)(ph - (long)p * H);
-  const float* e = in1 + (long)p * H * W;
-  const float* eq = q1 + (long)p * H * W;
-  float mu = 0.f;
-  for (int bh = 0; bh < bs; ++bh) {
-    const long r = (long)clampi(h + bh - half, 0, H - 1) * W;
-#pragma unroll
-    for (int bw = 0; bw < bs; ++bw) mu += eq[r + clampi(x + bw - half, 0, W - 1)];
-  }
-  float s = 0.f;
-  for (int bh = 0; bh < bs; ++bh) {
-    const long r = (long)clampi(h + bh - half, 0, H - 1) * W;
-#pragma unroll
-    for (int bw = 0; bw < bs; ++bw) {
-      const float v = e[r + clampi(x + bw - half, 0, W - 1)] - mu;
-      s += v * v;
-    }
-  }
-  pstat[i] = make_float2(mu, s);
 }
 
 // thread per pixel; the pattern taps of d+1, d, d-1 in row r are pr[clamp(base + j)], j = bw, bw + 1, bw + 2
@@ -218,20 +158,8 @@ static int xcorrvol_subpixel_f32(const float* in0, const float* in1, long in1_fr
                      bs2);
   CTD_LAUNCH_CHECK();
   if (!prepared) {
-    const long n1 = (long)P * HW;
-    hipLaunchKernelGGL(subpixel_quotient_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, stream, in1, q1, n1,
-                       bs2);
-    CTD_LAUNCH_CHECK();
-    const long ns = (long)P * H * ((long)W + D - 1);
-    const dim3 g((unsigned)((ns + 255) / 256));
-    switch (bs) {
-      case 3: hipLaunchKernelGGL(subpixel_pattern_stats_kernel<3>, g, dim3(256), 0, stream, in1, q1, pstat, P, H, W, D, bs); break;
-      case 5: hipLaunchKernelGGL(subpixel_pattern_stats_kernel<5>, g, dim3(256), 0, stream, in1, q1, pstat, P, H, W, D, bs); break;
-      case 7: hipLaunchKernelGGL(subpixel_pattern_stats_kernel<7>, g, dim3(256), 0, stream, in1, q1, pstat, P, H, W, D, bs); break;
-      case 9: hipLaunchKernelGGL(subpixel_pattern_stats_kernel<9>, g, dim3(256), 0, stream, in1, q1, pstat, P, H, W, D, bs); break;
-      default: hipLaunchKernelGGL(subpixel_pattern_stats_kernel<0>, g, dim3(256), 0, stream, in1, q1, pstat, P, H, W, D, bs); break;
-    }
-    CTD_LAUNCH_CHECK();
+    const int st = subpixel_fill_pattern_planes(in1, q1, pstat, P, H, W, D, bs, stream);
+    if (st != CTD_OK) return st;
   }
   const dim3 g((unsigned)((n0 + 255) / 256));
   switch (bs) {

@@ -904,6 +904,139 @@ costvol_subpixel.__doc__ += _SUBPIXEL_RULE
 
 
 # --------------------------------------------------------------------------------------
+# Band-limited matching: the best score within a per-pixel disparity range (additive; include/ctd_hip_band.h states
+# the definition word for word)
+# --------------------------------------------------------------------------------------
+_BAND_RULE = """
+    The definition (include/ctd_hip_band.h), on the reference-order volume V (NCC: xcorrvol(algo="exact"), higher is
+    better; costs: costvol(algo="exact"), lower is better): lo and hi are inclusive and clipped to [0, D-1],
+    lo' = max(lo, 0), hi' = min(hi, D-1); idx is the first index of the best V[f,d,h,w] over d in [lo', hi'], -1 when
+    lo' > hi'; best is V[f,idx,h,w] bit for bit, NaN where idx == -1.  No volume is read or written, any band width up
+    to D is legal, and a band of [0, D-1] everywhere returns the indices of torch.argmax / argmin of V."""
+
+
+def disparity_band(prior, radius, n_disps):
+    """Additive: the search range [lo, hi] (int32, shaped as `prior`, inclusive) of the band matchers around a
+    disparity prior -- a network's prediction, the previous frame's disparity, an upsampled coarse match.
+    prior f32 (any device, CPU included: pure torch); radius a float or a tensor broadcastable to prior.
+      lo = clamp(ceil(prior - radius), 0, D), hi = clamp(floor(prior + radius), -1, D - 1),
+    each one float32 subtraction / addition before the rounding.  A non-finite prior or a radius that is negative or NaN
+    gives lo = D, hi = -1: an empty band (idx -1, best NaN)."""
+    if not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32:
+        raise RuntimeError("disparity_band: prior must be a float32 tensor")
+    D = int(n_disps)
+    r = torch.as_tensor(radius, dtype=torch.float32, device=prior.device)
+    r = r.expand(prior.shape) if r.dim() else r
+    empty = ~torch.isfinite(prior) | ~(r >= 0)
+    lo = torch.ceil(prior - r).clamp(0, D)
+    hi = torch.floor(prior + r).clamp(-1, D - 1)
+    lo = torch.where(empty, torch.full_like(lo, D), lo).to(torch.int32)
+    hi = torch.where(empty, torch.full_like(hi, -1), hi).to(torch.int32)
+    return lo.contiguous(), hi.contiguous()
+
+
+def _band_range(lo, hi, shape, dev, who):
+    for t, name in ((lo, "lo"), (hi, "hi")):
+        _check(t, name, (torch.int32,))
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError("%s: %s must be int32 shaped %s" % (who, name, tuple(shape)))
+        if t.device != dev:
+            raise RuntimeError("%s: %s is on another device" % (who, name))
+
+
+def xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared=None, subpixel=None):
+    """Additive: NCC matching within a per-pixel disparity range, without a volume (C == 1).
+    in0 [N,1,H,W] | [1,H,W]; in1 [1,H,W] | [N,1,H,W] as `xcorrvol_argmax` takes them; lo, hi int32 [N,H,W] | [H,W]
+    (see `disparity_band`).  Returns (idx int64, best f32), shaped as lo.
+    `prepared`: a `prepare_pattern` handle of the same in1 and frame count keeps the pattern's window statistics -- the
+    planes `xcorrvol_subpixel` keeps there too, filled by whichever of the two ops runs first -- so later calls skip
+    the pattern half.
+    subpixel: None (default) | "parabola" | "equiangular": also return (disp f32, refined u8) of
+    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple (the fit runs through the volume's scores at
+    idx - 1 and idx + 1 whether or not they lie in the band; idx == -1 gives NaN / 0)."""
+    who = "xcorrvol_argmax_band"
+    if subpixel is not None:
+        _subpixel_mode(subpixel, who)
+        out = xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared)
+        return tuple(out) + xcorrvol_subpixel(in0, in1, out[0], n_disps, block_size, subpixel, prepared)
+    _check(in0, "in0", (torch.float32,))
+    _check(in1, "in1", (torch.float32,))
+    squeeze = in0.dim() == 3
+    a0 = in0.unsqueeze(0) if squeeze else in0
+    if a0.dim() != 4 or a0.shape[1] != 1 or in1.dim() not in (3, 4):
+        raise RuntimeError("%s expects in0 [N,1,H,W] or [1,H,W] and in1 [1,H,W] or [N,1,H,W]" % who)
+    dev = _same_device(a0, in1)
+    N, C, H, W = a0.shape
+    if tuple(in1.shape[-3:]) != (C, H, W) or (in1.dim() == 4 and in1.shape[0] != N):
+        raise RuntimeError("%s: in1 does not match in0" % who)
+    shape = (H, W) if squeeze else (N, H, W)
+    _band_range(lo, hi, shape, dev, who)
+    stride1 = 0 if in1.dim() == 3 else H * W
+    D, bs = int(n_disps), int(block_size)
+    idx = torch.empty(shape, dtype=torch.int64, device=dev)
+    best = torch.empty(shape, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nws = L.ctd_xcorrvol_argmax_band_workspace_bytes(N, H, W, D, bs, 1 if stride1 else 0)
+    flag = 0
+    if prepared is not None:
+        if prepared.in1 is not in1 or prepared.n_frames != N or prepared.workspace.device != dev:
+            raise RuntimeError("%s: `prepared` belongs to another pattern, frame count or device" % who)
+        key = (H, W, D, bs)
+        ws = prepared.subpixel.get(key)
+        if ws is None:
+            ws = prepared.subpixel[key] = _workspace(nws, dev)
+        else:
+            flag = 0x100                                                # CTD_PATTERN_PREPARED: the pattern planes are in ws
+    else:
+        ws = _workspace(nws, dev)
+    st = L.ctd_xcorrvol_argmax_band_f32(_ptr(a0), _ptr(in1), stride1, _ptr(lo), _ptr(hi), _ptr(idx), _ptr(best), N, H, W,
+                                        D, bs, flag, _ptr(ws), ws.numel(), dev.index, _stream(dev))
+    if st != 0 and flag == 0 and prepared is not None:
+        prepared.subpixel.pop((H, W, D, bs), None)                      # the planes were not written
+    _lib.check(st, who)
+    return idx, best
+
+
+def costvol_argmin_band(im, pattern, lo, hi, n_disps, block_size, type='census_sad', eps=0.1, subpixel=None):
+    """Additive: SAD / MSE / soft-census block matching within a per-pixel disparity range, without a volume.
+    im [N,H,W] | [H,W] f32, pattern [H,W] | [N,H,W] as `costvol_argmin` takes them; lo, hi int32 shaped as im (see
+    `disparity_band`).  Returns (idx int64, best f32), shaped as im.
+    subpixel: None (default) | "equiangular" | "parabola": also return (disp, refined) of
+    `costvol_subpixel(im, pattern, idx, ...)` at the end of the tuple."""
+    who = "costvol_argmin_band"
+    if subpixel is not None:
+        _subpixel_mode(subpixel, who)
+        out = costvol_argmin_band(im, pattern, lo, hi, n_disps, block_size, type, eps)
+        return tuple(out) + costvol_subpixel(im, pattern, out[0], n_disps, block_size, type, eps, subpixel)
+    _check(im, "im", (torch.float32,))
+    _check(pattern, "pattern", (torch.float32,))
+    type = type.lower()
+    if type not in _PHOTO_TYPES:
+        raise RuntimeError("%s: invalid loss type %r" % (who, type))
+    squeeze = im.dim() == 2
+    a = im.unsqueeze(0) if squeeze else im
+    if a.dim() != 3 or pattern.dim() not in (2, 3) or tuple(pattern.shape[-2:]) != tuple(a.shape[-2:]):
+        raise RuntimeError("%s expects im [N,H,W] or [H,W] and pattern [H,W] or [N,H,W]" % who)
+    dev = _same_device(a, pattern)
+    N, H, W = a.shape
+    if pattern.dim() == 3 and pattern.shape[0] != N:
+        raise RuntimeError("%s: pattern batch does not match im" % who)
+    _band_range(lo, hi, im.shape, dev, who)
+    stride = 0 if pattern.dim() == 2 else H * W
+    idx = torch.empty(im.shape, dtype=torch.int64, device=dev)
+    best = torch.empty(im.shape, dtype=torch.float32, device=dev)
+    st = _lib.lib().ctd_costvol_argmin_band_f32(_ptr(a), _ptr(pattern), stride, _ptr(lo), _ptr(hi), _ptr(idx), _ptr(best),
+                                                N, H, W, int(n_disps), int(block_size), _PHOTO_TYPES[type], float(eps),
+                                                dev.index, _stream(dev))
+    _lib.check(st, who)
+    return idx, best
+
+
+xcorrvol_argmax_band.__doc__ += _BAND_RULE
+costvol_argmin_band.__doc__ += _BAND_RULE
+
+
+# --------------------------------------------------------------------------------------
 # Match validity: left-right consistency and uniqueness (additive; include/ctd_hip.h states the rule word for word)
 # --------------------------------------------------------------------------------------
 VALID_IN_PATTERN, VALID_LR_OK, VALID_UNIQUE = 1, 2, 4
