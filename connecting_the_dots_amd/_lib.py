@@ -1,4 +1,5 @@
-"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h and ctd_hip_band.h).
+"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h and
+ctd_hip_warp.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -154,6 +155,15 @@ BAND_SIGNATURES = {
                                                                                                  _vp]),
 }
 
+# forward depth warping and the windowed band of include/ctd_hip_warp.h (an addition beside ctd_hip.h and ctd_hip_band.h;
+# torchext.depth_warp, torchext.disparity_band_window)
+WARP_SIGNATURES = {
+    "ctd_depth_warp_workspace_bytes": (_c_size_t, [_c_int] * 4),
+    "ctd_depth_warp_f32": (_c_int, [_vp] * 8 + [_c_int, _vp, _vp] + [_c_int] * 4 + [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_disparity_band_window_f32": (_c_int, [_vp, _c_float, _c_int, _c_int, _c_int, _vp, _vp] + [_c_int] * 3 +
+                                      [_c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -166,7 +176,8 @@ def lib():
                 "connecting_the_dots_amd: %s is missing -- build it with "
                 "`python -m connecting_the_dots_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
+                                  list(WARP_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

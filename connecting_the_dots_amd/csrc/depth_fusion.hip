@@ -3,8 +3,9 @@
 //
 // view_match() is the one place that projects a pixel of view r into view s, samples the nearest source pixel, projects
 // it back and decides consistency; the consistency pass and the emit pass of the fusion both call it, so the two cannot
-// drift apart.  Every product and sum is in the association of the header (that of geo_forward in losses.hip); the build
-// never contracts them.  Poses and K are indexed by block-uniform values only (track, view, loop counter): scalar loads.
+// drift apart.  live_at() and view_transform() are those of ctd_view.h, shared with depth_warp.hip.  Every product and
+// sum is in the association of the header (that of geo_forward in losses.hip); the build never contracts them.  Poses
+// and K are indexed by block-uniform values only (track, view, loop counter): scalar loads.
 //   depth_consistency_kernel -- a 64 x 4 tile of one view, thread = reference pixel, loop over the source views.
 //     Per pixel: 5 B read + 12 B ray, per source view one 5 B gather + 12 B ray of the pixel hit; 6 B written.
 //   fuse_count_kernel   -- 256 consecutive pixels of ONE view (a chunk never crosses a view, so the pose stays uniform
@@ -17,6 +18,7 @@
 //     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
 // Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
 #include "ctd_common.h"
+#include "ctd_view.h"
 
 namespace ctd {
 namespace {
@@ -27,26 +29,6 @@ constexpr int kScan = 1024;                                   // threads of the 
 struct FuseTol {
   float max_px2, max_rel;                                     // max_px * max_px (one f32 product), max_rel
 };
-
-__device__ inline bool live_at(const float* __restrict__ depth, const uint8_t* __restrict__ valid, long g) {
-  const float d = depth[g];
-  return (!valid || valid[g]) && d > 0.f && d < __builtin_inff();
-}
-
-// depth d along ray3 in view a -> uvd in view b (X_cam = R X_world + t)
-__device__ inline void view_transform(const float* __restrict__ ray3, float d, const float* __restrict__ Ra,
-                                      const float* __restrict__ ta, const float* __restrict__ Rb,
-                                      const float* __restrict__ tb, const float* __restrict__ K, float* uvd) {
-  float p[3], q[3], s[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) p[i] = d * ray3[i] - ta[i];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) q[j] = p[0] * Ra[0 * 3 + j] + p[1] * Ra[1 * 3 + j] + p[2] * Ra[2 * 3 + j];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) s[j] = q[0] * Rb[j * 3 + 0] + q[1] * Rb[j * 3 + 1] + q[2] * Rb[j * 3 + 2] + tb[j];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) uvd[j] = s[0] * K[j * 3 + 0] + s[1] * K[j * 3 + 1] + s[2] * K[j * 3 + 2];
-}
 
 // Steps a, b, c of the header for the live pixel (x, y) of view r, depth d_r, against view s of the same track
 // (depth, valid, R, t point at the track).  true = consistent; q = the source pixel of step a, z = z' of step b.

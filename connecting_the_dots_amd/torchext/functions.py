@@ -1381,7 +1381,8 @@ _DEPTH_FUSION_RULE = """
     count >= min_views, fused = (depth + the z' of the consistent views, ascending) / (1 + count), NaN where not kept."""
 
 
-def _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views, who):
+def _track_inputs(depth, ray, K, R, t, valid, who):
+    """the tensors of a track of posed views -> (device, valid as uint8 or None)"""
     ts = [_f32(x, n) for x, n in ((depth, "depth"), (ray, "ray"), (K, "K"), (R, "R"), (t, "t"))]
     dev = _same_device(*ts)
     if depth.dim() != 4 or min(depth.shape[1:]) == 0:
@@ -1398,6 +1399,11 @@ def _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views,
             raise RuntimeError("%s: valid must have the shape of depth" % who)
         _same_device(depth, valid)
         v = valid.view(torch.uint8)
+    return dev, v
+
+
+def _depth_fusion_inputs(depth, ray, K, R, t, valid, max_px, max_rel, min_views, who):
+    dev, v = _track_inputs(depth, ray, K, R, t, valid, who)
     if not all(isinstance(x, numbers.Real) and 0.0 <= x < float("inf") for x in (max_px, max_rel)):
         raise RuntimeError("%s: max_px and max_rel must be finite numbers >= 0" % who)
     max_px, max_rel = float(max_px), float(max_rel)
@@ -1459,6 +1465,122 @@ def depth_fuse_points(depth, ray, K, R, t, valid=None, max_px=1.0, max_rel=0.01,
 
 depth_consistency.__doc__ += _DEPTH_FUSION_RULE
 depth_fuse_points.__doc__ += _DEPTH_FUSION_RULE
+
+
+# --------------------------------------------------------------------------------------
+# Forward depth warping and the windowed band: from the views matched so far to the search range of the next one
+# (additive; include/ctd_hip_warp.h states both definitions word for word)
+# --------------------------------------------------------------------------------------
+_DEPTH_WARP_RULE = """
+    The definition (include/ctd_hip_warp.h).  depth, ray, K, R, t, valid and "live" are those of `depth_consistency`.
+    For a target view r with targets[b,r] != 0, every live pixel q = (yq, xq) of every view s != r with
+    sources[b,s] != 0 is transformed into r, uvd = transform(depth, ray[q], R_s, t_s, R_r, t_r, K) in the association of
+    the consistency rule; it is dropped unless 0 < uvd2 < inf; xs = floor(uvd0 / uvd2 + 0.5), ys likewise (f32); it is
+    dropped unless -splat <= xs <= W-1+splat and -splat <= ys <= H-1+splat (f32 compares, a NaN fails them); it is a
+    candidate for every (ys+dy, xs+dx), |dy|, |dx| <= splat, inside the image.  At a target pixel the candidate with the
+    smallest (z = uvd2, s*H*W + q) wins: z is its uvd2 bit for bit, src = ((b*V + s)*H + yq)*W + xq (the flat index of
+    `depth_fuse_points`).  No candidate, targets[b,r] == 0 or V == 1: z = NaN, src = -1.  The winner is an unsigned
+    minimum of (bits(z) << 32) | (s*H*W + q), so the same bits come out on every run.
+    The nearest surface wins, so a gross foreground outlier in a source view wins too: pass valid = keep of
+    `depth_consistency` for the views you warp from."""
+
+_BAND_WINDOW_RULE = """
+    The definition (include/ctd_hip_warp.h).  Over the window x window pixels around a pixel, clipped to the image, m
+    and M are the minimum and the maximum of the finite priors.  With at least one: lo = clamp(ceil(m - radius), 0, D),
+    hi = clamp(floor(M + radius), -1, D - 1), each one float32 subtraction / addition before the rounding.  With none:
+    holes="empty" gives lo = D, hi = -1, holes="full" gives lo = 0, hi = D - 1.  A radius that is negative or NaN gives
+    the empty band everywhere.  window=1, holes="empty" is `disparity_band(prior, radius, n_disps)` bit for bit."""
+
+_BAND_HOLES = {"empty": 0, "full": 1}
+
+
+def _view_mask(m, name, depth, who):
+    """a [B,V] view mask as uint8 (None: all views); its dtype and shape are checked before any device is looked at"""
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor) or m.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("%s: %s must be a bool or uint8 tensor" % (who, name))
+    if not isinstance(depth, torch.Tensor) or tuple(m.shape) != tuple(depth.shape[:2]):
+        raise RuntimeError("%s: %s must be shaped [B,V] as depth [B,V,H,W]" % (who, name))
+    return m.view(torch.uint8)
+
+
+def depth_warp(depth, ray, K, R, t, valid=None, sources=None, targets=None, splat=0, return_src=False):
+    """Additive: what every view of a track should look like given the track's other views -- a z-buffered forward warp
+    -> z f32 [B,V,H,W] (NaN where nothing lands), and with return_src (z, src int64 [B,V,H,W]) (-1 there).
+    sources, targets: bool / uint8 [B,V] or None (all): the views warped from and the views warped into (warp views
+    0..k-1 into view k with sources[:, :k] and targets[:, k] set).  splat 0, 1 or 2: every source pixel covers the
+    (2*splat+1)^2 pixels around where it lands, which closes the cracks between splats.  Not differentiable."""
+    who = "depth_warp"
+    if isinstance(splat, bool) or not isinstance(splat, numbers.Integral) or not 0 <= splat <= 2:
+        raise RuntimeError("%s: splat must be 0, 1 or 2" % who)
+    ms = _view_mask(sources, "sources", depth, who)
+    mt = _view_mask(targets, "targets", depth, who)
+    dev, v = _track_inputs(depth, ray, K, R, t, valid, who)
+    B, V, H, W = depth.shape
+    for m, name in ((ms, "sources"), (mt, "targets")):
+        if m is not None:
+            _check(m, name, (torch.uint8,))
+            _same_device(depth, m)
+    z = torch.empty(depth.shape, dtype=torch.float32, device=dev)
+    src = torch.empty(depth.shape, dtype=torch.int64, device=dev) if return_src else None
+    if B > 0:
+        L = _lib.lib()
+        ws = _workspace(L.ctd_depth_warp_workspace_bytes(B, V, H, W), dev)
+        st = L.ctd_depth_warp_f32(_ptr(depth), _ptr(v), _ptr(ray), _ptr(K), _ptr(R), _ptr(t), _ptr(ms), _ptr(mt), int(splat),
+                                  _ptr(z), _ptr(src), B, V, H, W, _ptr(ws), ws.numel(), dev.index, _stream(dev))
+        _lib.check(st, who)
+    return (z, src) if return_src else z
+
+
+def disparity_band_window(prior, radius, n_disps, window=3, holes="full"):
+    """Additive: the search range [lo, hi] (int32, shaped as `prior`, inclusive) of the band matchers around a disparity
+    prior that has holes and occlusion edges, such as `depth_to_disp(depth_warp(...))`: the band of a pixel spans every
+    finite prior of its window, so an edge keeps both the foreground and the background disparity and a crack is
+    filled from its neighbours.  prior f32 [N,H,W] | [H,W] on the GPU; radius a float; window odd, 1..15; holes "full"
+    (a window without any finite prior searches everything) | "empty" (it searches nothing: idx -1)."""
+    who = "disparity_band_window"
+    if isinstance(window, bool) or not isinstance(window, numbers.Integral) or not 1 <= window <= 15 or window % 2 == 0:
+        raise RuntimeError("%s: window must be an odd integer in [1, 15]" % who)
+    if holes not in _BAND_HOLES:
+        raise RuntimeError("%s: holes must be 'full' or 'empty', not %r" % (who, holes))
+    if isinstance(n_disps, bool) or not isinstance(n_disps, numbers.Integral) or n_disps < 1:
+        raise RuntimeError("%s: n_disps must be an integer >= 1" % who)
+    if not isinstance(radius, numbers.Real):
+        raise RuntimeError("%s: radius must be a number" % who)
+    if not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32:
+        raise RuntimeError("%s: prior must be a float32 tensor" % who)
+    if prior.dim() not in (2, 3) or min(prior.shape[-2:]) == 0:
+        raise RuntimeError("%s expects prior [N,H,W] or [H,W] with H, W >= 1" % who)
+    _check(prior, "prior", (torch.float32,))
+    dev = prior.device
+    H, W = prior.shape[-2:]
+    N = prior.shape[0] if prior.dim() == 3 else 1
+    lo = torch.empty(prior.shape, dtype=torch.int32, device=dev)
+    hi = torch.empty(prior.shape, dtype=torch.int32, device=dev)
+    if N > 0:
+        st = _lib.lib().ctd_disparity_band_window_f32(_ptr(prior), float(radius), int(n_disps), int(window),
+                                                      _BAND_HOLES[holes], _ptr(lo), _ptr(hi), N, H, W, dev.index,
+                                                      _stream(dev))
+        _lib.check(st, who)
+    return lo, hi
+
+
+def depth_to_disp(depth, baseline_focal, disp_offset=0.0):
+    """Additive: the inverse of `idx_to_depth`, `baseline_focal / depth - disp_offset` in float32 (one division, one
+    subtraction), NaN where depth is not finite and > 0 -- so the holes of `depth_warp` stay holes.  Pure torch, any
+    device.  Not differentiable."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
+        raise RuntimeError("depth_to_disp: depth must be a float32 tensor")
+    with torch.no_grad():
+        live = torch.isfinite(depth) & (depth > 0)
+        d = torch.where(live, depth, torch.ones_like(depth))
+        disp = torch.full_like(d, float(baseline_focal)) / d - float(disp_offset)
+        return torch.where(live, disp, torch.full_like(disp, float("nan")))
+
+
+depth_warp.__doc__ += _DEPTH_WARP_RULE
+disparity_band_window.__doc__ += _BAND_WINDOW_RULE
 
 
 # --------------------------------------------------------------------------------------
