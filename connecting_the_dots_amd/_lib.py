@@ -1,5 +1,5 @@
-"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h and
-ctd_hip_warp.h).
+"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
+ctd_hip_warp.h and ctd_hip_band_validity.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -164,6 +164,15 @@ WARP_SIGNATURES = {
                                       [_c_int, _vp]),
 }
 
+# match validity of the band matchers of include/ctd_hip_band_validity.h (an addition beside the headers above;
+# torchext.xcorrvol_band_validity, torchext.costvol_band_validity)
+BAND_VALIDITY_SIGNATURES = {
+    "ctd_xcorrvol_band_validity_f32": (_c_int, [_vp, _vp, _c_long] + [_vp] * 7 + [_c_int] * 6 + [_c_float, _c_int, _vp,
+                                                                                             _c_size_t, _c_int, _vp]),
+    "ctd_costvol_band_validity_f32": (_c_int, [_vp, _vp, _c_long] + [_vp] * 7 + [_c_int] * 6 + [_c_float, _c_int,
+                                                                                            _c_float, _c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -177,7 +186,7 @@ def lib():
                 "`python -m connecting_the_dots_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
-                                  list(WARP_SIGNATURES.items())):
+                                  list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

@@ -820,6 +820,28 @@ def _subpixel_outputs(idx):
         torch.empty(idx.shape, dtype=torch.uint8, device=idx.device)
 
 
+def _pattern_planes_workspace(prepared, who, in1, N, H, W, D, bs, nws, dev):
+    """(workspace, flag) of the ops that keep the pattern's window statistics in the band / sub-pixel workspace
+    (xcorrvol_subpixel, xcorrvol_argmax_band, xcorrvol_band_validity): a fresh one, or the one the `prepare_pattern`
+    handle keeps per (H, W, D, block) -- with CTD_PATTERN_PREPARED once an earlier call has filled its planes."""
+    if prepared is None:
+        return _workspace(nws, dev), 0
+    if prepared.in1 is not in1 or prepared.n_frames != N or prepared.workspace.device != dev:
+        raise RuntimeError("%s: `prepared` belongs to another pattern, frame count or device" % who)
+    key = (H, W, D, bs)
+    ws = prepared.subpixel.get(key)
+    if ws is None:
+        ws = prepared.subpixel[key] = _workspace(nws, dev)
+        return ws, 0
+    return ws, 0x100                                                    # CTD_PATTERN_PREPARED: the pattern planes are in ws
+
+
+def _pattern_planes_check(st, who, prepared, flag, H, W, D, bs):
+    if st != 0 and flag == 0 and prepared is not None:
+        prepared.subpixel.pop((H, W, D, bs), None)                      # the planes were not written
+    _lib.check(st, who)
+
+
 def xcorrvol_subpixel(in0, in1, idx, n_disps, block_size, mode="parabola", prepared=None):
     """Additive: sub-pixel refinement of NCC matcher indices -> (disp f32, refined u8), shaped as idx.
     in0 [N,1,H,W] | [1,H,W] and in1 [1,H,W] | [N,1,H,W] as `xcorrvol_argmax` takes them, idx int64 [N,H,W] | [H,W] as it
@@ -847,23 +869,10 @@ def xcorrvol_subpixel(in0, in1, idx, n_disps, block_size, mode="parabola", prepa
     D, bs = int(n_disps), int(block_size)
     L = _lib.lib()
     nws = L.ctd_xcorrvol_subpixel_workspace_bytes(N, H, W, D, bs, 1 if stride1 else 0)
-    flag = 0
-    if prepared is not None:
-        if prepared.in1 is not in1 or prepared.n_frames != N or prepared.workspace.device != dev:
-            raise RuntimeError("xcorrvol_subpixel: `prepared` belongs to another pattern, frame count or device")
-        key = (H, W, D, bs)
-        ws = prepared.subpixel.get(key)
-        if ws is None:
-            ws = prepared.subpixel[key] = _workspace(nws, dev)
-        else:
-            flag = 0x100                                                # CTD_PATTERN_PREPARED: the pattern planes are in ws
-    else:
-        ws = _workspace(nws, dev)
+    ws, flag = _pattern_planes_workspace(prepared, "xcorrvol_subpixel", in1, N, H, W, D, bs, nws, dev)
     st = L.ctd_xcorrvol_subpixel_f32(_ptr(a0), _ptr(in1), stride1, _ptr(idx), _ptr(disp), _ptr(refined), N, H, W, D, bs,
                                      m | flag, _ptr(ws), ws.numel(), dev.index, _stream(dev))
-    if st != 0 and flag == 0 and prepared is not None:
-        prepared.subpixel.pop((H, W, D, bs), None)                      # the planes were not written
-    _lib.check(st, "xcorrvol_subpixel")
+    _pattern_planes_check(st, "xcorrvol_subpixel", prepared, flag, H, W, D, bs)
     return disp, refined
 
 
@@ -944,21 +953,8 @@ def _band_range(lo, hi, shape, dev, who):
             raise RuntimeError("%s: %s is on another device" % (who, name))
 
 
-def xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared=None, subpixel=None):
-    """Additive: NCC matching within a per-pixel disparity range, without a volume (C == 1).
-    in0 [N,1,H,W] | [1,H,W]; in1 [1,H,W] | [N,1,H,W] as `xcorrvol_argmax` takes them; lo, hi int32 [N,H,W] | [H,W]
-    (see `disparity_band`).  Returns (idx int64, best f32), shaped as lo.
-    `prepared`: a `prepare_pattern` handle of the same in1 and frame count keeps the pattern's window statistics -- the
-    planes `xcorrvol_subpixel` keeps there too, filled by whichever of the two ops runs first -- so later calls skip
-    the pattern half.
-    subpixel: None (default) | "parabola" | "equiangular": also return (disp f32, refined u8) of
-    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple (the fit runs through the volume's scores at
-    idx - 1 and idx + 1 whether or not they lie in the band; idx == -1 gives NaN / 0)."""
-    who = "xcorrvol_argmax_band"
-    if subpixel is not None:
-        _subpixel_mode(subpixel, who)
-        out = xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared)
-        return tuple(out) + xcorrvol_subpixel(in0, in1, out[0], n_disps, block_size, subpixel, prepared)
+def _ncc_band_inputs(in0, in1, lo, hi, who):
+    """checks of the NCC band ops -> (a0 [N,1,H,W], output shape, in1 frame stride, device)"""
     _check(in0, "in0", (torch.float32,))
     _check(in1, "in1", (torch.float32,))
     squeeze = in0.dim() == 3
@@ -971,29 +967,53 @@ def xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared=None, s
         raise RuntimeError("%s: in1 does not match in0" % who)
     shape = (H, W) if squeeze else (N, H, W)
     _band_range(lo, hi, shape, dev, who)
-    stride1 = 0 if in1.dim() == 3 else H * W
+    return a0, shape, (0 if in1.dim() == 3 else H * W), dev
+
+
+def _cost_band_inputs(im, pattern, lo, hi, type, who):
+    """checks of the cost band ops -> (a [N,H,W], type code, pattern frame stride, device)"""
+    _check(im, "im", (torch.float32,))
+    _check(pattern, "pattern", (torch.float32,))
+    type = type.lower()
+    if type not in _PHOTO_TYPES:
+        raise RuntimeError("%s: invalid loss type %r" % (who, type))
+    squeeze = im.dim() == 2
+    a = im.unsqueeze(0) if squeeze else im
+    if a.dim() != 3 or pattern.dim() not in (2, 3) or tuple(pattern.shape[-2:]) != tuple(a.shape[-2:]):
+        raise RuntimeError("%s expects im [N,H,W] or [H,W] and pattern [H,W] or [N,H,W]" % who)
+    dev = _same_device(a, pattern)
+    if pattern.dim() == 3 and pattern.shape[0] != a.shape[0]:
+        raise RuntimeError("%s: pattern batch does not match im" % who)
+    _band_range(lo, hi, im.shape, dev, who)
+    return a, _PHOTO_TYPES[type], (0 if pattern.dim() == 2 else a.shape[1] * a.shape[2]), dev
+
+
+def xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared=None, subpixel=None):
+    """Additive: NCC matching within a per-pixel disparity range, without a volume (C == 1).
+    in0 [N,1,H,W] | [1,H,W]; in1 [1,H,W] | [N,1,H,W] as `xcorrvol_argmax` takes them; lo, hi int32 [N,H,W] | [H,W]
+    (see `disparity_band`).  Returns (idx int64, best f32), shaped as lo.
+    `prepared`: a `prepare_pattern` handle of the same in1 and frame count keeps the pattern's window statistics -- the
+    planes `xcorrvol_subpixel` and `xcorrvol_band_validity` keep there too, filled by whichever op runs first -- so
+    later calls skip the pattern half.
+    subpixel: None (default) | "parabola" | "equiangular": also return (disp f32, refined u8) of
+    `xcorrvol_subpixel(in0, in1, idx, ...)` at the end of the tuple (the fit runs through the volume's scores at
+    idx - 1 and idx + 1 whether or not they lie in the band; idx == -1 gives NaN / 0)."""
+    who = "xcorrvol_argmax_band"
+    if subpixel is not None:
+        _subpixel_mode(subpixel, who)
+        out = xcorrvol_argmax_band(in0, in1, lo, hi, n_disps, block_size, prepared)
+        return tuple(out) + xcorrvol_subpixel(in0, in1, out[0], n_disps, block_size, subpixel, prepared)
+    a0, shape, stride1, dev = _ncc_band_inputs(in0, in1, lo, hi, who)
+    N, _, H, W = a0.shape
     D, bs = int(n_disps), int(block_size)
     idx = torch.empty(shape, dtype=torch.int64, device=dev)
     best = torch.empty(shape, dtype=torch.float32, device=dev)
     L = _lib.lib()
     nws = L.ctd_xcorrvol_argmax_band_workspace_bytes(N, H, W, D, bs, 1 if stride1 else 0)
-    flag = 0
-    if prepared is not None:
-        if prepared.in1 is not in1 or prepared.n_frames != N or prepared.workspace.device != dev:
-            raise RuntimeError("%s: `prepared` belongs to another pattern, frame count or device" % who)
-        key = (H, W, D, bs)
-        ws = prepared.subpixel.get(key)
-        if ws is None:
-            ws = prepared.subpixel[key] = _workspace(nws, dev)
-        else:
-            flag = 0x100                                                # CTD_PATTERN_PREPARED: the pattern planes are in ws
-    else:
-        ws = _workspace(nws, dev)
+    ws, flag = _pattern_planes_workspace(prepared, who, in1, N, H, W, D, bs, nws, dev)
     st = L.ctd_xcorrvol_argmax_band_f32(_ptr(a0), _ptr(in1), stride1, _ptr(lo), _ptr(hi), _ptr(idx), _ptr(best), N, H, W,
                                         D, bs, flag, _ptr(ws), ws.numel(), dev.index, _stream(dev))
-    if st != 0 and flag == 0 and prepared is not None:
-        prepared.subpixel.pop((H, W, D, bs), None)                      # the planes were not written
-    _lib.check(st, who)
+    _pattern_planes_check(st, who, prepared, flag, H, W, D, bs)
     return idx, best
 
 
@@ -1008,26 +1028,13 @@ def costvol_argmin_band(im, pattern, lo, hi, n_disps, block_size, type='census_s
         _subpixel_mode(subpixel, who)
         out = costvol_argmin_band(im, pattern, lo, hi, n_disps, block_size, type, eps)
         return tuple(out) + costvol_subpixel(im, pattern, out[0], n_disps, block_size, type, eps, subpixel)
-    _check(im, "im", (torch.float32,))
-    _check(pattern, "pattern", (torch.float32,))
-    type = type.lower()
-    if type not in _PHOTO_TYPES:
-        raise RuntimeError("%s: invalid loss type %r" % (who, type))
-    squeeze = im.dim() == 2
-    a = im.unsqueeze(0) if squeeze else im
-    if a.dim() != 3 or pattern.dim() not in (2, 3) or tuple(pattern.shape[-2:]) != tuple(a.shape[-2:]):
-        raise RuntimeError("%s expects im [N,H,W] or [H,W] and pattern [H,W] or [N,H,W]" % who)
-    dev = _same_device(a, pattern)
+    a, ty, stride, dev = _cost_band_inputs(im, pattern, lo, hi, type, who)
     N, H, W = a.shape
-    if pattern.dim() == 3 and pattern.shape[0] != N:
-        raise RuntimeError("%s: pattern batch does not match im" % who)
-    _band_range(lo, hi, im.shape, dev, who)
-    stride = 0 if pattern.dim() == 2 else H * W
     idx = torch.empty(im.shape, dtype=torch.int64, device=dev)
     best = torch.empty(im.shape, dtype=torch.float32, device=dev)
     st = _lib.lib().ctd_costvol_argmin_band_f32(_ptr(a), _ptr(pattern), stride, _ptr(lo), _ptr(hi), _ptr(idx), _ptr(best),
-                                                N, H, W, int(n_disps), int(block_size), _PHOTO_TYPES[type], float(eps),
-                                                dev.index, _stream(dev))
+                                                N, H, W, int(n_disps), int(block_size), ty, float(eps), dev.index,
+                                                _stream(dev))
     _lib.check(st, who)
     return idx, best
 
@@ -1066,6 +1073,75 @@ def _validity_outputs(idx):
     dev = idx.device
     return (torch.empty(idx.shape, dtype=torch.uint8, device=dev), torch.empty(idx.shape, dtype=torch.int64, device=dev),
             torch.empty(idx.shape, dtype=torch.float32, device=dev))
+
+
+_BAND_VALIDITY_RULE = """
+    The definition (include/ctd_hip_band_validity.h), on the reference-order volume V of the band functions: pixel
+    (f,h,w) *holds* d when lo' <= d <= hi' (lo' = max(lo, 0), hi' = min(hi, D-1)).
+      idx, best    exactly those of the band function (-1 / NaN on an empty band)
+      idx_r[f,h,x] first index of the best V[f,d,h,x+d] over those d in [0, min(D, W-x)) that pixel x+d holds; -1 when no
+                   pixel holds a disparity that lands on column x; ties go to the smaller d (-0.0 and +0.0 tie)
+      gap[f,h,w]   s1 - s2 (NCC) | s2 - s1 (costs), s1 = V[idx], s2 = the best V[d] over held d with |d - idx| >= 2; +inf
+                   when no such d is held, NaN when idx == -1.  A band of width <= 3 around idx always passes UNIQUE.
+      flags bit 0 IN_PATTERN: idx >= 0 and w - idx >= 0;  bit 1 LR_OK: bit 0 and |idx_r[f,h,w-idx] - idx| <= lr_tol;
+            bit 2 UNIQUE: idx >= 0 and gap > min_gap;  valid = (flags == 7).
+    With lo = 0, hi = D-1 everywhere flags, idx_r and gap are those of `match_validity` on V with the returned idx.
+    Every output is exact (the reference's bits) and the same on every run; no volume is read or written.  Unlike
+    `xcorrvol_validity` / `costvol_validity` on a band function's idx, the pattern side sees only what the bands hold."""
+
+
+def xcorrvol_band_validity(in0, in1, lo, hi, n_disps, block_size, lr_tol=1, min_gap=0.0, prepared=None, subpixel=None):
+    """Additive: `xcorrvol_argmax_band` with the validity of its matches within the band -> (idx int64, best f32,
+    flags u8, idx_r int64, gap f32), each shaped as lo.  Inputs, `prepared` (the handle's planes now serve three ops:
+    `xcorrvol_subpixel`, `xcorrvol_argmax_band` and this one) and `subpixel` (appends (disp, refined)) as there.
+    Use: disparity_filter(idx.float(), flags == 7)."""
+    who = "xcorrvol_band_validity"
+    if subpixel is not None:
+        _subpixel_mode(subpixel, who)
+        out = xcorrvol_band_validity(in0, in1, lo, hi, n_disps, block_size, lr_tol, min_gap, prepared)
+        return tuple(out) + xcorrvol_subpixel(in0, in1, out[0], n_disps, block_size, subpixel, prepared)
+    lr_tol, min_gap = _validity_params(lr_tol, min_gap, who)
+    a0, shape, stride1, dev = _ncc_band_inputs(in0, in1, lo, hi, who)
+    N, _, H, W = a0.shape
+    D, bs = int(n_disps), int(block_size)
+    idx = torch.empty(shape, dtype=torch.int64, device=dev)
+    best = torch.empty(shape, dtype=torch.float32, device=dev)
+    flags, idx_r, gap = _validity_outputs(idx)
+    L = _lib.lib()
+    nws = L.ctd_xcorrvol_argmax_band_workspace_bytes(N, H, W, D, bs, 1 if stride1 else 0)
+    ws, flag = _pattern_planes_workspace(prepared, who, in1, N, H, W, D, bs, nws, dev)
+    st = L.ctd_xcorrvol_band_validity_f32(_ptr(a0), _ptr(in1), stride1, _ptr(lo), _ptr(hi), _ptr(idx), _ptr(best),
+                                          _ptr(flags), _ptr(idx_r), _ptr(gap), N, H, W, D, bs, lr_tol, min_gap, flag,
+                                          _ptr(ws), ws.numel(), dev.index, _stream(dev))
+    _pattern_planes_check(st, who, prepared, flag, H, W, D, bs)
+    return idx, best, flags, idx_r, gap
+
+
+def costvol_band_validity(im, pattern, lo, hi, n_disps, block_size, type='census_sad', eps=0.1, lr_tol=1, min_gap=0.0,
+                          subpixel=None):
+    """Additive: `costvol_argmin_band` with the validity of its matches within the band -> (idx int64, best f32,
+    flags u8, idx_r int64, gap f32), each shaped as im.  Inputs and `subpixel` (appends (disp, refined)) as there."""
+    who = "costvol_band_validity"
+    if subpixel is not None:
+        _subpixel_mode(subpixel, who)
+        out = costvol_band_validity(im, pattern, lo, hi, n_disps, block_size, type, eps, lr_tol, min_gap)
+        return tuple(out) + costvol_subpixel(im, pattern, out[0], n_disps, block_size, type, eps, subpixel)
+    lr_tol, min_gap = _validity_params(lr_tol, min_gap, who)
+    a, ty, stride, dev = _cost_band_inputs(im, pattern, lo, hi, type, who)
+    N, H, W = a.shape
+    idx = torch.empty(im.shape, dtype=torch.int64, device=dev)
+    best = torch.empty(im.shape, dtype=torch.float32, device=dev)
+    flags, idx_r, gap = _validity_outputs(idx)
+    st = _lib.lib().ctd_costvol_band_validity_f32(_ptr(a), _ptr(pattern), stride, _ptr(lo), _ptr(hi), _ptr(idx),
+                                                  _ptr(best), _ptr(flags), _ptr(idx_r), _ptr(gap), N, H, W, int(n_disps),
+                                                  int(block_size), ty, float(eps), lr_tol, min_gap, dev.index,
+                                                  _stream(dev))
+    _lib.check(st, who)
+    return idx, best, flags, idx_r, gap
+
+
+xcorrvol_band_validity.__doc__ += _BAND_VALIDITY_RULE
+costvol_band_validity.__doc__ += _BAND_VALIDITY_RULE
 
 
 def _validity_rescored(ws, P, dev):
