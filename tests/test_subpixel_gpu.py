@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import workloads
+from tests.subpixel_ref import fit_reference
 from tests.util import golden
 
 pytestmark = pytest.mark.gpu
@@ -24,44 +25,6 @@ def te():
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def fit_reference(vol, idx, maximum, mode):
-    """the rule of include/ctd_hip.h on the CPU in float32: vol [N,D,H,W], idx [N,H,W] -> (disp, refined u8)"""
-    vol, idx = vol.detach().cpu(), idx.detach().cpu()
-    D = vol.shape[1]
-    valid = (idx >= 0) & (idx < D)
-    inner = valid & (idx > 0) & (idx < D - 1)
-    ic = idx.clamp(0, D - 1)
-
-    def at(k):
-        return vol.gather(1, (ic + k).clamp(0, D - 1).unsqueeze(1)).squeeze(1)
-
-    m, z, p = at(-1), at(0), at(1)
-    half = torch.tensor(0.5, dtype=torch.float32)
-    if maximum:
-        if mode == "parabola":
-            den = (m - z) + (p - z)
-            ok = den < 0
-            delta = half * ((m - p) / den)
-        else:
-            q = torch.where(p > m, z - m, z - p)
-            ok = q > 0
-            delta = half * ((p - m) / q)
-    else:
-        if mode == "parabola":
-            den = (m - z) + (p - z)
-            ok = den > 0
-            delta = half * ((m - p) / den)
-        else:
-            q = torch.where(p < m, m - z, p - z)
-            ok = q > 0
-            delta = half * ((m - p) / q)
-    ok = ok & inner
-    d = ic.to(torch.float32)
-    disp = torch.where(ok, d + delta.clamp(-0.5, 0.5), d)
-    disp = torch.where(valid, disp, torch.tensor(float("nan")))
-    return disp, ok.to(torch.uint8)
 
 
 def assert_bits(disp, refined, ref, what=""):
