@@ -1,5 +1,5 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h and ctd_hip_band_validity.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h and ctd_hip_icp.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -173,6 +173,16 @@ BAND_VALIDITY_SIGNATURES = {
                                                                                             _c_float, _c_int, _vp]),
 }
 
+# depth-map normals and point-to-plane ICP of include/ctd_hip_icp.h (an addition beside the headers above;
+# torchext.depth_normals, torchext.depth_icp_system, torchext.depth_icp_update, torchext.depth_icp)
+ICP_SIGNATURES = {
+    "ctd_depth_normals_f32": (_c_int, [_vp] * 3 + [_c_float, _vp] + [_c_int] * 4 + [_c_int, _vp]),
+    "ctd_depth_icp_workspace_bytes": (_c_size_t, [_c_int] * 4),
+    "ctd_depth_icp_system_f32": (_c_int, [_vp] * 8 + [_c_float] + [_vp] * 3 + [_c_int] * 4 + [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_depth_icp_update_f32": (_c_int, [_vp] * 4 + [_c_int, ctypes.c_double, ctypes.c_double] + [_vp] * 3 +
+                                 [_c_int] * 2 + [_c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -186,7 +196,8 @@ def lib():
                 "`python -m connecting_the_dots_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
-                                  list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items())):
+                                  list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
+                                  list(ICP_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

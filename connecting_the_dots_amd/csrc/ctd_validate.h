@@ -20,6 +20,22 @@ inline bool img_shape_ok(int B, int H, int W) {
   return B > 0 && H > 0 && W > 0 && B <= 65535 && (double)B * H * W < 2147483648.0;
 }
 
+// a buffer of a call, for the overlap check of the entry points that state one (depth_fusion.hip, depth_icp.hip)
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+// true when one of the first n_out spans (the buffers a call writes) shares a byte with any other span; NULL spans are absent
+inline bool spans_overlap(const Span* s, int n_out, int n) {
+  for (int i = 0; i < n_out; ++i)
+    for (int j = 0; j < n; ++j) {
+      if (j == i || (j < n_out && j < i) || !s[i].p || !s[j].p || !s[i].bytes || !s[j].bytes) continue;
+      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) return true;
+    }
+  return false;
+}
+
 }  // namespace ctd
 
 // ctd_photometric_{fwd,bwd}_<SFX> over the launchers photometric_{fwd,bwd}_<SFX> of the including file

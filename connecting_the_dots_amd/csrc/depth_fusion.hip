@@ -18,6 +18,7 @@
 //     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
 // Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
 #include "ctd_common.h"
+#include "ctd_validate.h"
 #include "ctd_view.h"
 
 namespace ctd {
@@ -273,21 +274,6 @@ static bool depth_fusion_sizes_ok(int B, int V, int H, int W) {
 static bool depth_fusion_params_ok(float max_px, float max_rel, int min_views) {
   const float big = 3.402823466e38f;                                                          // (a NaN fails >=)
   return max_px >= 0.f && max_px <= big && max_rel >= 0.f && max_rel <= big && min_views >= 0 && min_views <= 255;
-}
-
-struct Span {
-  const void* p;
-  size_t bytes;
-};
-// true when one of the first n_out spans (the buffers a call writes) shares a byte with any other span; NULL spans are absent
-static bool spans_overlap(const Span* s, int n_out, int n) {
-  for (int i = 0; i < n_out; ++i)
-    for (int j = 0; j < n; ++j) {
-      if (j == i || (j < n_out && j < i) || !s[i].p || !s[j].p || !s[i].bytes || !s[j].bytes) continue;
-      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
-      if (a < b + s[j].bytes && b < a + s[i].bytes) return true;
-    }
-  return false;
 }
 
 int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,

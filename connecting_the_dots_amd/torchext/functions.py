@@ -1660,6 +1660,214 @@ disparity_band_window.__doc__ += _BAND_WINDOW_RULE
 
 
 # --------------------------------------------------------------------------------------
+# Depth-map normals and projective point-to-plane ICP: from slightly wrong poses back to ones that the consistency check
+# confirms (additive; include/ctd_hip_icp.h states the three rules word for word)
+# --------------------------------------------------------------------------------------
+_DEPTH_NORMALS_RULE = """
+    The rule (include/ctd_hip_icp.h).  depth, ray, valid and "live" are those of `depth_consistency`.  A pixel (y, x)
+    with 1 <= x <= W-2, 1 <= y <= H-2 gets a normal when it and its four axis neighbours are live and every neighbour's
+    depth satisfies |d_nb - d| <= max_rel * d.  P(q) = d(q) * ray[q]; a = P(y,x+1) - P(y,x-1), b = P(y+1,x) - P(y-1,x);
+    c = a x b, each component as a1*b2 - a2*b1; l = sqrt(c0*c0 + c1*c1 + c2*c2); no normal unless 0 < l < inf; n = c / l,
+    negated when n . P(y,x) > 0, so that it faces the camera.  Every other pixel gets three NaNs.  All float32,
+    uncontracted, no atomics: the same bits on every run."""
+
+_DEPTH_ICP_RULE = """
+    The rule (include/ctd_hip_icp.h).  depth, ray, K, R, t, valid and "live" are those of `depth_consistency`; normal is
+    `depth_normals(depth, ray, valid)`.  View s of track b is aligned to view a = target[b,s] (int32 [B,V]; None: every
+    view s >= 1 to view 0); a value outside 0..V-1 or equal to s skips the view: a system of zeros, residual NaN,
+    assoc -1, pose unchanged.  A live pixel q of view s gives S, its point in the frame of camera a, and uvd = K S (the
+    products and sums of the consistency rule); it is dropped unless uvd2 > 0, unless xs = floor(uvd0 / uvd2 + 0.5),
+    ys likewise, lie inside the image, unless p = ys*W + xs is live in view a and normal[b,a,p] is finite, and unless
+    D = S - d_a(p) * ray[p] has |D|^2 <= max_dist^2.  Then n = normal[b,a,p], e = n . D and J = (S x n, n).
+    system float64 [B,V,29] = the 21 upper-triangle entries of sum J J^T (row-major), the 6 of sum J e, sum e^2 and the
+    count; every product is exact in float64 and the order of every sum is fixed: the same bits on every run.
+    residual = e, assoc = ((b*V + a)*H + ys)*W + xs, NaN / -1 where the pixel was dropped.
+    The update, one view at a time in float64: A from the triangle with A_ii += damping * A_ii, factored L D L^T; the
+    view is left unchanged (R' = R, t' = t bit for bit, ok = 0) when it is skipped, when count < min_count, or when a
+    pivot is not finite or <= min_pivot * A_ii (A_ii undamped) -- the sign of a surface that does not constrain all six
+    degrees of freedom, a single plane for one.  Otherwise xi = (omega, v) = -A^-1 g, Rr = exp([omega]x) by Rodrigues
+    (the series below an angle of 1e-4), tr = v, and the new pose of s is the one for which every S becomes Rr S + tr
+    while view a stays: [R_a|t_a] [R_s'|t_s']^-1 = [Rr|tr] [R_a|t_a] [R_s|t_s]^-1, rounded to float32 once; ok = 1.  R is
+    not re-orthonormalised."""
+
+
+def _icp_number(x, name, who):
+    if isinstance(x, bool) or not isinstance(x, numbers.Real) or not 0.0 <= x < float("inf"):
+        raise RuntimeError("%s: %s must be a finite number >= 0" % (who, name))
+    return float(x)
+
+
+def _icp_count(x, name, who, lo=0):
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not lo <= x < 2 ** 31:
+        raise RuntimeError("%s: %s must be an integer >= %d" % (who, name, lo))
+    return int(x)
+
+
+def _icp_target(target, B, V, dev, who):
+    """target as int32 [B,V] on the device of the track (None stays None: every view s >= 1 to view 0)"""
+    if target is None:
+        return None
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int32:
+        raise RuntimeError("%s: target must be an int32 tensor" % who)
+    if tuple(target.shape) != (B, V):
+        raise RuntimeError("%s: target must be shaped [B,V]" % who)
+    _check(target, "target", (torch.int32,))
+    if target.device != dev:
+        raise RuntimeError("all tensors must be on the same device (%s vs %s)" % (dev, target.device))
+    return target
+
+
+def _icp_normal(normal, depth, who):
+    _f32(normal, "normal")
+    if not isinstance(depth, torch.Tensor) or tuple(normal.shape) != tuple(depth.shape) + (3,):
+        raise RuntimeError("%s: normal must be shaped [B,V,H,W,3] as depth [B,V,H,W]" % who)
+    return normal
+
+
+def depth_normals(depth, ray, valid=None, max_rel=0.02):
+    """Additive: the surface normal at every pixel of a track's depth maps, in the frame of the pixel's own camera and
+    facing it -> normal f32 [B,V,H,W,3], three NaNs where a pixel has none (the image border, holes, depth edges).  With
+    the points `depth[..., None] * ray` these are the oriented points a mesher takes.  Not differentiable."""
+    who = "depth_normals"
+    max_rel = _icp_number(max_rel, "max_rel", who)
+    ts = [_f32(depth, "depth"), _f32(ray, "ray")]
+    dev = _same_device(*ts)
+    if depth.dim() != 4 or min(depth.shape[1:]) == 0:
+        raise RuntimeError("%s expects depth [B,V,H,W] with V, H, W >= 1" % who)
+    B, V, H, W = depth.shape
+    if V > 64:
+        raise RuntimeError("%s: at most 64 views" % who)
+    if ray.numel() != H * W * 3:
+        raise RuntimeError("%s: ray [H*W,3] expected" % who)
+    v = None
+    if valid is not None:
+        _check(valid, "valid", (torch.bool, torch.uint8))
+        if valid.shape != depth.shape:
+            raise RuntimeError("%s: valid must have the shape of depth" % who)
+        _same_device(depth, valid)
+        v = valid.view(torch.uint8)
+    normal = torch.empty(tuple(depth.shape) + (3,), dtype=torch.float32, device=dev)
+    if B > 0:
+        st = _lib.lib().ctd_depth_normals_f32(_ptr(depth), _ptr(v), _ptr(ray), max_rel, _ptr(normal), B, V, H, W, dev.index,
+                                              _stream(dev))
+        _lib.check(st, who)
+    return normal
+
+
+def _icp_system_call(depth, v, normal, ray, K, R, t, target, max_dist, return_maps, dev, who):
+    """one launch of the system on validated inputs -> (system, residual or None, assoc or None)"""
+    B, V, H, W = depth.shape
+    system = torch.empty((B, V, 29), dtype=torch.float64, device=dev)
+    residual = torch.empty(depth.shape, dtype=torch.float32, device=dev) if return_maps else None
+    assoc = torch.empty(depth.shape, dtype=torch.int64, device=dev) if return_maps else None
+    if B > 0:
+        L = _lib.lib()
+        ws = _workspace(L.ctd_depth_icp_workspace_bytes(B, V, H, W), dev)
+        st = L.ctd_depth_icp_system_f32(_ptr(depth), _ptr(v), _ptr(normal), _ptr(ray), _ptr(K), _ptr(R), _ptr(t),
+                                        _ptr(target), max_dist, _ptr(system), _ptr(residual), _ptr(assoc), B, V, H, W,
+                                        _ptr(ws), ws.numel(), dev.index, _stream(dev))
+        _lib.check(st, who)
+    return system, residual, assoc
+
+
+def _icp_pose_shapes(R, t, B, V, who):
+    """R [B,V,3,3] and t [B,V,3] exactly: the update sizes its launch and its outputs by them"""
+    if not isinstance(R, torch.Tensor) or not isinstance(t, torch.Tensor) or tuple(R.shape) != (B, V, 3, 3) or \
+            tuple(t.shape) != (B, V, 3):
+        raise RuntimeError("%s: R must be shaped [B,V,3,3] and t [B,V,3]" % who)
+
+
+def _icp_update_call(system, R, t, target, min_count, min_pivot, damping, B, V, dev, who):
+    """one launch of the update on validated inputs: system [B,V,29], R [B,V,3,3], t [B,V,3]"""
+    R_out, t_out = torch.empty_like(R), torch.empty_like(t)
+    ok = torch.empty((B, V), dtype=torch.uint8, device=dev)
+    if B > 0:
+        st = _lib.lib().ctd_depth_icp_update_f32(_ptr(system), _ptr(R), _ptr(t), _ptr(target), min_count, min_pivot, damping,
+                                                 _ptr(R_out), _ptr(t_out), _ptr(ok), B, V, dev.index, _stream(dev))
+        _lib.check(st, who)
+    return R_out, t_out, ok
+
+
+def depth_icp_system(depth, normal, ray, K, R, t, valid=None, target=None, max_dist=0.1, return_maps=False):
+    """Additive: the normal equations of one round of projective point-to-plane ICP that aligns views of a track to
+    other views of it -> system float64 [B,V,29], and with return_maps (system, residual f32 [B,V,H,W], assoc int64
+    [B,V,H,W]).  Feed it to `depth_icp_update`; `depth_icp` runs both in a loop.  Not differentiable."""
+    who = "depth_icp_system"
+    max_dist = _icp_number(max_dist, "max_dist", who)
+    dev, v = _track_inputs(depth, ray, K, R, t, valid, who)
+    B, V = depth.shape[:2]
+    _icp_normal(normal, depth, who)
+    _same_device(depth, normal)
+    target = _icp_target(target, B, V, dev, who)
+    system, residual, assoc = _icp_system_call(depth, v, normal, ray, K, R, t, target, max_dist, return_maps, dev, who)
+    return (system, residual, assoc) if return_maps else system
+
+
+def _icp_update_inputs(system, R, t, target, who):
+    _check(system, "system", (torch.float64,))
+    dev = _same_device(system, _f32(R, "R"), _f32(t, "t"))
+    if R.dim() != 4 or tuple(R.shape[2:]) != (3, 3) or R.shape[1] == 0:
+        raise RuntimeError("%s expects R [B,V,3,3] with V >= 1" % who)
+    B, V = R.shape[:2]
+    if V > 64:
+        raise RuntimeError("%s: at most 64 views" % who)
+    if tuple(t.shape) != (B, V, 3) or tuple(system.shape) != (B, V, 29):
+        raise RuntimeError("%s: system [B,V,29], R [B,V,3,3], t [B,V,3] expected" % who)
+    return dev, B, V, _icp_target(target, B, V, dev, who)
+
+
+def depth_icp_update(system, R, t, target=None, min_count=64, min_pivot=1e-4, damping=0.0):
+    """Additive: solves the systems of `depth_icp_system` and moves the poses -> (R' f32 [B,V,3,3], t' f32 [B,V,3],
+    ok uint8 [B,V]); R and t are not written.  `target` must be the one the system was built with.  Not
+    differentiable."""
+    who = "depth_icp_update"
+    min_count = _icp_count(min_count, "min_count", who)
+    min_pivot = _icp_number(min_pivot, "min_pivot", who)
+    damping = _icp_number(damping, "damping", who)
+    dev, B, V, target = _icp_update_inputs(system, R, t, target, who)
+    return _icp_update_call(system, R, t, target, min_count, min_pivot, damping, B, V, dev, who)
+
+
+def depth_icp(depth, ray, K, R, t, valid=None, target=None, iters=10, max_rel=0.02, max_dist=0.1, min_count=64,
+              min_pivot=1e-4, damping=0.0):
+    """Additive: refines the poses of a track's views by projective point-to-plane ICP between its depth maps
+    -> (R' f32 [B,V,3,3], t' f32 [B,V,3], info).  `depth_normals(depth, ray, valid, max_rel)` once, then `iters` rounds of
+    `depth_icp_system` and `depth_icp_update` on the current stream, without any host synchronisation.  info, all device
+    tensors: "count" and "rmse" float64 [iters,B,V], the number of pixels and sqrt(sum e^2 / count) of the system each
+    round solved (NaN where the count is 0), and "ok" uint8 [B,V] of the last round.  target=None aligns every view
+    s >= 1 to view 0.  It converges from errors of a few degrees and centimetres on surfaces that constrain all six degrees
+    of freedom; on a single plane every round leaves the poses as they are (ok = 0).  Not differentiable."""
+    who = "depth_icp"
+    iters = _icp_count(iters, "iters", who, 1)
+    max_rel = _icp_number(max_rel, "max_rel", who)
+    max_dist = _icp_number(max_dist, "max_dist", who)
+    min_count = _icp_count(min_count, "min_count", who)
+    min_pivot = _icp_number(min_pivot, "min_pivot", who)
+    damping = _icp_number(damping, "damping", who)
+    if isinstance(depth, torch.Tensor) and depth.dim() == 4:              # (anything else: _track_inputs says so)
+        _icp_pose_shapes(R, t, depth.shape[0], depth.shape[1], who)
+    dev, v = _track_inputs(depth, ray, K, R, t, valid, who)
+    B, V = depth.shape[:2]
+    target = _icp_target(target, B, V, dev, who)
+    normal = depth_normals(depth, ray, valid, max_rel)
+    systems = []
+    ok = torch.zeros((B, V), dtype=torch.uint8, device=dev)
+    for _ in range(iters):
+        system = _icp_system_call(depth, v, normal, ray, K, R, t, target, max_dist, False, dev, who)[0]
+        R, t, ok = _icp_update_call(system, R, t, target, min_count, min_pivot, damping, B, V, dev, who)
+        systems.append(system)
+    systems = torch.stack(systems)
+    count = systems[..., 28]
+    return R, t, {"count": count, "rmse": torch.sqrt(systems[..., 27] / count), "ok": ok}
+
+
+depth_normals.__doc__ += _DEPTH_NORMALS_RULE
+depth_icp_system.__doc__ += _DEPTH_ICP_RULE
+depth_icp_update.__doc__ += _DEPTH_ICP_RULE
+depth_icp.__doc__ += _DEPTH_ICP_RULE
+
+
+# --------------------------------------------------------------------------------------
 # Fused loss kernels (reference: stock-PyTorch modules of model/networks.py; additive API)
 # --------------------------------------------------------------------------------------
 def _f32(t, name):
