@@ -1,5 +1,5 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h and ctd_hip_icp.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h and ctd_hip_tsdf.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -183,6 +183,17 @@ ICP_SIGNATURES = {
                                  [_c_int] * 2 + [_c_int, _vp]),
 }
 
+# truncated signed distance volumes of include/ctd_hip_tsdf.h (an addition beside the headers above;
+# torchext.tsdf_volume, torchext.tsdf_integrate, torchext.tsdf_surface_points, torchext.tsdf_raycast)
+TSDF_SIGNATURES = {
+    "ctd_tsdf_integrate_f32": (_c_int, [_vp] * 3 + [_c_float] + [_vp] * 6 + [_c_float, _c_float] + [_c_int] * 7 + [_c_int, _vp]),
+    "ctd_tsdf_surface_workspace_bytes": (_c_size_t, [_c_int] * 4),
+    "ctd_tsdf_surface_points_f32": (_c_int, [_vp] * 3 + [_c_float, _c_float] + [_vp] * 4 + [ctypes.c_int64] + [_c_int] * 4 +
+                                    [_vp, _c_size_t, _c_int, _vp]),
+    "ctd_tsdf_raycast_f32": (_c_int, [_vp] * 3 + [_c_float] + [_vp] * 3 + [_c_float, _c_float, _c_int, _c_float, _vp] +
+                             [_c_int] * 7 + [_c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -197,7 +208,7 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
-                                  list(ICP_SIGNATURES.items())):
+                                  list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

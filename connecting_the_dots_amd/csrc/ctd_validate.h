@@ -20,7 +20,7 @@ inline bool img_shape_ok(int B, int H, int W) {
   return B > 0 && H > 0 && W > 0 && B <= 65535 && (double)B * H * W < 2147483648.0;
 }
 
-// a buffer of a call, for the overlap check of the entry points that state one (depth_fusion.hip, depth_icp.hip)
+// a buffer of a call, for the overlap check of the entry points that state one (depth_fusion.hip, depth_icp.hip, tsdf.hip)
 struct Span {
   const void* p;
   size_t bytes;

@@ -1,4 +1,4 @@
-// ctd_view.h -- the device helpers every multi-view kernel shares (depth_fusion.hip, depth_warp.hip, depth_icp.hip): which pixels
+// ctd_view.h -- the device helpers every multi-view kernel shares (depth_fusion.hip, depth_warp.hip, depth_icp.hip, tsdf.hip): which pixels
 // of a depth map are live, and the projection of a pixel of one posed view into another.  Every product and sum of
 // view_transform is in the association of include/ctd_hip.h (that of geo_forward in losses.hip); the build never
 // contracts them, so every kernel that includes this header computes the same bits.

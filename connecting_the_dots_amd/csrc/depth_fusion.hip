@@ -12,12 +12,13 @@
 //     and the workgroups are in ascending `src` order): the emit flag (with dedupe: the projections into the views
 //     s < r again, and keep of the pixel hit) and, from one ballot per wavefront, the workgroup's number of flags.
 //     Per pixel: 1 B read + 1 B written; with dedupe, for a kept pixel, 4 + 12 B and per earlier view 5 + 12 + 1 B.
-//   fuse_scan_kernel    -- ONE workgroup: exclusive scan of the workgroup counts, 1024 at a time with a carry, then the
-//     per-track totals as differences of the scanned offsets.
+//   fuse_scan_kernel    -- (ctd_scan.h, shared with tsdf.hip) ONE workgroup: exclusive scan of the workgroup counts,
+//     1024 at a time with a carry, then the per-track totals as differences of the scanned offsets.
 //   fuse_scatter_kernel -- the chunks again: offset of the workgroup + flags before the lane (ballot), and for a flagged
 //     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
 // Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
 #include "ctd_common.h"
+#include "ctd_scan.h"
 #include "ctd_validate.h"
 #include "ctd_view.h"
 
@@ -25,7 +26,6 @@ namespace ctd {
 namespace {
 
 constexpr int kChunk = 256;                                   // pixels per workgroup of the count and scatter kernels
-constexpr int kScan = 1024;                                   // threads of the scan workgroup
 
 struct FuseTol {
   float max_px2, max_rel;                                     // max_px * max_px (one f32 product), max_rel
@@ -134,39 +134,6 @@ __global__ __launch_bounds__(kChunk) void fuse_count_kernel(
   if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
   __syncthreads();
   if (threadIdx.x == 0) wg_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-}
-
-// offsets[i] = counts[0] + ... + counts[i-1] for i = 0 .. n (the scan may run in place); n_per_track from the offsets
-__global__ __launch_bounds__(kScan) void fuse_scan_kernel(int* offsets, int n, int per_track, int64_t* __restrict__ n_per_track,
-                                                          int B) {
-  __shared__ int wave_sum[kScan / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += kScan) {
-    const int i = base + tid;
-    const int v = i < n ? offsets[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScan / 64; ++w) {
-      before += w < wave ? wave_sum[w] : 0;
-      total += wave_sum[w];
-    }
-    if (i < n) offsets[i] = carry + before + incl - v;
-    carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) offsets[n] = carry;
-  __syncthreads();                                            // the offsets this workgroup wrote are read back below
-  for (int b = tid; b < B; b += kScan)
-    n_per_track[b] = (int64_t)(offsets[(long)(b + 1) * per_track] - offsets[(long)b * per_track]);
 }
 
 __global__ __launch_bounds__(kChunk) void fuse_scatter_kernel(
