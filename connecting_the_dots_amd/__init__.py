@@ -3,6 +3,14 @@
 `connecting_the_dots_amd.torchext` mirrors the reference's `torchext.functions` /
 `torchext.modules` API (torchext/functions.py, torchext/modules.py); the arithmetic runs in
 hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
+
+    torchext.functions   the import surface: every op by name, nothing else (`__all__`)
+    torchext.modules     the nn.Module wrappers (CoordConv2d, LCN, the loss modules)
+    torchext.<family>    the wrappers themselves, one module per kernel family: nn_ops, ncc, lcn_ops, photometric,
+                         costvol_ops, subpixel, validity, band, sgm, disp_filter, multiview, tsdf, losses; what they
+                         share is in torchext._common (checks, launch plumbing) and torchext._track (posed views)
+    _lib                 ctypes binding of libctd_hip.so; build: `python -m connecting_the_dots_amd.build`
+    synth, renderer, hyperdepth, nets, train, sharding   the data, model and training side above torchext
 """
 from . import torchext  # noqa: F401
 

@@ -1,7 +1,11 @@
 """Mirror of the reference's `torchext/modules.py` (CoordConv2d, modules.py:7-27)."""
 import torch
 
+from . import functions
 from .functions import *  # noqa: F401,F403  (the reference re-exports functions here, modules.py:5)
+
+__all__ = functions.__all__ + ["CoordConv2d", "DispToDepth", "DisparityLoss", "LCN", "MultiScalePatternSimilarityLoss",
+                               "ProjectionDepthSimilarityLoss", "RectifiedPatternSimilarityLoss"]
 
 
 class CoordConv2d(torch.nn.Module):

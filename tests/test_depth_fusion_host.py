@@ -252,26 +252,24 @@ def test_timing_tool_host_parts(tmp_path):
     assert "NOT MEASURED" in tool.kernel_lines(shape, 1000, None)[0]
 
 
-def test_wrapper_rejects_odd_parameters_with_runtime_error():
+def test_wrapper_rejects_odd_parameters_with_runtime_error(monkeypatch):
     """the parameter checks come after the tensor checks, so they are reached with a fake `depth` only through the
     helper; every bad value raises RuntimeError like the neighbouring ops, never ValueError / TypeError / OverflowError"""
-    from connecting_the_dots_amd.torchext import functions as F_
+    from connecting_the_dots_amd.torchext import _track, multiview
     import torch
 
-    real = (F_._f32, F_._same_device)
-    F_._f32, F_._same_device = (lambda x, n: x), (lambda *ts: torch.device("cpu"))
-    try:
-        sc = fr.make_scene("clean", 1, 2, 5, 7, 0)
-        a = [torch.from_numpy(sc[k]) for k in ("depth", "ray", "K", "R", "t")]
-        ok = F_._depth_fusion_inputs(*a, None, 1, np.float32(0.01), np.int64(2), "x")
-        assert ok[2:] == (1.0, float(np.float32(0.01)), 2)
-        for bad in (dict(min_views=float("nan")), dict(min_views=float("inf")), dict(min_views=None), dict(min_views="1"),
-                    dict(min_views=1.5), dict(min_views=-1), dict(min_views=256), dict(max_px=None), dict(max_px="1"),
-                    dict(max_px=float("nan")), dict(max_px=float("inf")), dict(max_px=-1.0), dict(max_rel=None),
-                    dict(max_rel=float("inf")), dict(max_rel=-0.1)):
-            kw = dict(max_px=1.0, max_rel=0.01, min_views=1)
-            kw.update(bad)
-            with pytest.raises(RuntimeError):
-                F_._depth_fusion_inputs(*a, None, kw["max_px"], kw["max_rel"], kw["min_views"], "x")
-    finally:
-        F_._f32, F_._same_device = real
+    # the tensor checks that `_depth_fusion_inputs` runs first live in `_track_inputs`: let CPU tensors through them
+    monkeypatch.setattr(_track, "_f32", lambda x, n: x)
+    monkeypatch.setattr(_track, "_same_device", lambda *ts: torch.device("cpu"))
+    sc = fr.make_scene("clean", 1, 2, 5, 7, 0)
+    a = [torch.from_numpy(sc[k]) for k in ("depth", "ray", "K", "R", "t")]
+    ok = multiview._depth_fusion_inputs(*a, None, 1, np.float32(0.01), np.int64(2), "x")
+    assert ok[2:] == (1.0, float(np.float32(0.01)), 2)
+    for bad in (dict(min_views=float("nan")), dict(min_views=float("inf")), dict(min_views=None), dict(min_views="1"),
+                dict(min_views=1.5), dict(min_views=-1), dict(min_views=256), dict(max_px=None), dict(max_px="1"),
+                dict(max_px=float("nan")), dict(max_px=float("inf")), dict(max_px=-1.0), dict(max_rel=None),
+                dict(max_rel=float("inf")), dict(max_rel=-0.1)):
+        kw = dict(max_px=1.0, max_rel=0.01, min_views=1)
+        kw.update(bad)
+        with pytest.raises(RuntimeError):
+            multiview._depth_fusion_inputs(*a, None, kw["max_px"], kw["max_rel"], kw["min_views"], "x")
