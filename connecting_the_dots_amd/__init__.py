@@ -11,6 +11,7 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          share is in torchext._common (checks, launch plumbing) and torchext._track (posed views)
     _lib                 ctypes binding of libctd_hip.so; build: `python -m connecting_the_dots_amd.build`
     synth, renderer, hyperdepth, nets, train, sharding   the data, model and training side above torchext
+    mesh                 the triangle mesh of a TSDF volume (include/ctd_hip_mesh.h) for renderer.MeshBVH, and PLY files
 """
 from . import torchext  # noqa: F401
 

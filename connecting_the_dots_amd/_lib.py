@@ -1,5 +1,5 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h and ctd_hip_tsdf.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h and ctd_hip_mesh.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -194,6 +194,14 @@ TSDF_SIGNATURES = {
                              [_c_int] * 7 + [_c_int, _vp]),
 }
 
+# marching cubes over a volume of include/ctd_hip_mesh.h (an addition beside the headers above; mesh.tsdf_mesh)
+MESH_SIGNATURES = {
+    "ctd_tsdf_mesh_workspace_bytes": (_c_size_t, [_c_int] * 4),
+    "ctd_tsdf_mesh_faces_i32": (_c_int, [_vp, _vp, _c_float, _vp, _vp, ctypes.c_int64] + [_c_int] * 4 + [_vp, _c_size_t, _c_int,
+                                                                                                    _vp]),
+    "ctd_tsdf_mesh_case": (_c_int, [_c_int, ctypes.POINTER(ctypes.c_int32)]),
+}
+
 _lib = None
 
 
@@ -208,7 +216,8 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
-                                  list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items())):
+                                  list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
+                                  list(MESH_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args
