@@ -12,6 +12,8 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
     _lib                 ctypes binding of libctd_hip.so; build: `python -m connecting_the_dots_amd.build`
     synth, renderer, hyperdepth, nets, train, sharding   the data, model and training side above torchext
     mesh                 the triangle mesh of a TSDF volume (include/ctd_hip_mesh.h) for renderer.MeshBVH, and PLY files
+    meshops              mesh clean-up (include/ctd_hip_mesh_clean.h): connected components, removal of small components,
+                         of faces with coincident vertices and of unreferenced vertices, compaction
 """
 from . import torchext  # noqa: F401
 

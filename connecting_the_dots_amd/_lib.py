@@ -1,5 +1,5 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h and ctd_hip_mesh.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h and ctd_hip_mesh_clean.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -202,6 +202,16 @@ MESH_SIGNATURES = {
     "ctd_tsdf_mesh_case": (_c_int, [_c_int, ctypes.POINTER(ctypes.c_int32)]),
 }
 
+# mesh clean-up of include/ctd_hip_mesh_clean.h (an addition beside the headers above; meshops.mesh_components,
+# meshops.mesh_clean, meshops.clean_tsdf_mesh)
+_c_i64 = ctypes.c_int64
+MESH_CLEAN_SIGNATURES = {
+    "ctd_mesh_clean_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
+    "ctd_mesh_components_i32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _c_size_t, _c_int, _vp]),
+    "ctd_mesh_clean_i32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp,
+                                    _c_size_t, _c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -217,7 +227,7 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
-                                  list(MESH_SIGNATURES.items())):
+                                  list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

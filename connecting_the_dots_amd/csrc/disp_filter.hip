@@ -20,6 +20,7 @@
 //   in registers and selects by counting ranks (ties in window raster order; a NaN tap compares false, so dead taps
 //   never take part).
 #include "ctd_common.h"
+#include "ctd_union_find.h"
 
 namespace ctd {
 namespace {
@@ -38,32 +39,7 @@ __device__ inline float load_live(const float* __restrict__ disp, const uint8_t*
 // both live (a dead pixel is NaN and fails the compare) and within max_diff: one f32 subtraction
 __device__ inline bool linked(float a, float b, float max_diff) { return fabsf(a - b) <= max_diff; }
 
-template <int SCOPE>
-__device__ inline int uf_find(int* L, int x) {                // path halving; every write is an atomic min
-  for (;;) {
-    const int p1 = __hip_atomic_load(L + x, __ATOMIC_RELAXED, SCOPE);
-    if (p1 == x) return x;
-    const int p2 = __hip_atomic_load(L + p1, __ATOMIC_RELAXED, SCOPE);
-    if (p2 == p1) return p1;
-    __hip_atomic_fetch_min(L + x, p2, __ATOMIC_RELAXED, SCOPE);
-    x = p2;
-  }
-}
-
-template <int SCOPE>
-__device__ inline void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find<SCOPE>(L, a);
-    b = uf_find<SCOPE>(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = __hip_atomic_fetch_min(L + b, a, __ATOMIC_RELAXED, SCOPE);
-    if (old == b) return;                                     // b was a root: hung under a
-    b = old;                                                  // b had a parent already: join a with that one
-  }
-}
-
-constexpr int kWg = __HIP_MEMORY_SCOPE_WORKGROUP, kAgent = __HIP_MEMORY_SCOPE_AGENT;
+// uf_find, uf_union, uf_count_runs and the scopes kWg, kAgent: ctd_union_find.h (shared with mesh_clean.hip)
 
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTile) void cc_tile_kernel(const float* __restrict__ disp, const uint8_t* __restrict__ valid,
@@ -155,7 +131,6 @@ __global__ __launch_bounds__(256) void cc_seam_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int* __restrict__ root, int* count, long plane,
                                                          long pixels) {
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   long key = -1;                                               // the root as an index into the whole batch
   if (g < pixels) {
     const long fo = g / plane * plane;
@@ -166,11 +141,7 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int* __res
     }
     root[g] = rt;
   }
-  // one add per run of equal roots inside the wavefront
-  const long prev = __shfl_up(key, 1);
-  const bool head = lane == 0 || key != prev;
-  const unsigned long long rest = (__ballot(head) >> lane) >> 1;
-  if (head && key >= 0) atomicAdd(count + key, rest ? __ffsll(rest) : 64 - lane);
+  uf_count_runs(count, key);                                   // one add per run of equal roots inside the wavefront
 }
 
 __global__ __launch_bounds__(256) void cc_finish_kernel(const int* __restrict__ root, const int* __restrict__ count,
