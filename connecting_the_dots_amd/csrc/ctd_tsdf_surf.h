@@ -1,15 +1,15 @@
 // ctd_tsdf_surf.h -- what tsdf.hip (the surface points) and tsdf_mesh.hip (the faces over those points) share: the
-// chunking of a track's voxels, the usability rule of include/ctd_hip_tsdf.h, the crossing-flag count kernel and the
-// checks of a grid's sizes.  The faces index the points, so both files must flag, count and order the crossings with
-// the same code: it lives here once.
+// voxel of a thread, the usability rule of include/ctd_hip_tsdf.h, the crossing-flag count kernel and the checks of a
+// grid's sizes.  The faces index the points, so both files must flag, count and order the crossings with the same
+// code: it lives here once, over the chunks and the prefixes of ctd_compact.h.
 #pragma once
 
 #include "ctd_common.h"
+#include "ctd_compact.h"
+#include "ctd_validate.h"
 
 namespace ctd {
 namespace {
-
-constexpr int kSurfChunk = 256;                               // voxels per workgroup of the count and scatter kernels
 
 struct Grid {
   int nx, ny, nz;
@@ -21,9 +21,10 @@ struct SurfVoxel {
   long p, g;
 };
 __device__ inline SurfVoxel surf_voxel_of_block(Grid gr, long nvox, int chunks) {
+  const ChunkItem c = chunk_item(chunks);
   SurfVoxel s;
-  s.b = blockIdx.x / chunks;
-  s.p = (long)(blockIdx.x % chunks) * kSurfChunk + threadIdx.x;
+  s.b = c.group;
+  s.p = c.p;
   s.g = (long)s.b * nvox + s.p;
   s.i = (int)(s.p % gr.nx);
   s.j = (int)((s.p / gr.nx) % gr.ny);
@@ -39,11 +40,11 @@ __device__ inline bool surf_usable(const float* __restrict__ tsdf, const float* 
   return fabsf(T) < 1.f;
 }
 
-__global__ __launch_bounds__(kSurfChunk) void surf_count_kernel(const float* __restrict__ tsdf,
-                                                                const float* __restrict__ weight, float min_weight,
-                                                                uint8_t* __restrict__ emit, int* __restrict__ wg_count,
-                                                                Grid gr, long nvox, int chunks) {
-  __shared__ int wave_n[kSurfChunk / 64];
+__global__ __launch_bounds__(kChunk) void surf_count_kernel(const float* __restrict__ tsdf,
+                                                            const float* __restrict__ weight, float min_weight,
+                                                            uint8_t* __restrict__ emit, int* __restrict__ wg_count, Grid gr,
+                                                            long nvox, int chunks) {
+  __shared__ int wave_n[kChunk / 64];
   const SurfVoxel s = surf_voxel_of_block(gr, nvox, chunks);
   int f = 0;
   if (s.p < nvox) {
@@ -60,15 +61,12 @@ __global__ __launch_bounds__(kSurfChunk) void surf_count_kernel(const float* __r
     }
     emit[s.g] = (uint8_t)f;
   }
-  const int n = __popcll(__ballot(f & 1)) + __popcll(__ballot(f & 2)) + __popcll(__ballot(f & 4));
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) wg_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+  int total;
+  (void)wg_flags3_before<kChunk>(f, wave_n, total);
+  if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
 }
 
-inline long surf_chunks(int nx, int ny, int nz) { return ((long)nx * ny * nz + kSurfChunk - 1) / kSurfChunk; }
-
-inline bool positive_finite(float v) { return v > 0.f && v < __builtin_inff(); }   // (a NaN fails the compares)
+inline long surf_chunks(int nx, int ny, int nz) { return chunks_of((long)nx * ny * nz); }
 
 // 0 ok, else the status of the first failing check of the grid's sizes
 inline int grid_status(int B, int nx, int ny, int nz, bool invalid_only) {
@@ -79,11 +77,9 @@ inline int grid_status(int B, int nx, int ny, int nz, bool invalid_only) {
 }
 
 inline int surf_shape_status(int B, int nx, int ny, int nz) {
-  int st = grid_status(B, nx, ny, nz, true);
+  const int st = grid_status(B, nx, ny, nz, false);
   if (st != CTD_OK) return st;
-  st = grid_status(B, nx, ny, nz, false);
-  if (st != CTD_OK) return st;
-  if (3.0 * B * nx * ny * nz >= 2147483648.0 || (double)B * surf_chunks(nx, ny, nz) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (3.0 * B * nx * ny * nz >= 2147483648.0 || !launch_ok((double)B * surf_chunks(nx, ny, nz))) return CTD_ERR_UNSUPPORTED;
   return CTD_OK;
 }
 

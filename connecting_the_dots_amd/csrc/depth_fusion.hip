@@ -3,29 +3,27 @@
 //
 // view_match() is the one place that projects a pixel of view r into view s, samples the nearest source pixel, projects
 // it back and decides consistency; the consistency pass and the emit pass of the fusion both call it, so the two cannot
-// drift apart.  live_at() and view_transform() are those of ctd_view.h, shared with depth_warp.hip.  Every product and
-// sum is in the association of the header (that of geo_forward in losses.hip); the build never contracts them.  Poses
+// drift apart.  live_at(), view_transform() and camera_to_world() are those of ctd_view.h, where every product and sum
+// is in the association of the header; the chunks, the workgroup prefix and the scan are those of ctd_compact.h.  Poses
 // and K are indexed by block-uniform values only (track, view, loop counter): scalar loads.
 //   depth_consistency_kernel -- a 64 x 4 tile of one view, thread = reference pixel, loop over the source views.
 //     Per pixel: 5 B read + 12 B ray, per source view one 5 B gather + 12 B ray of the pixel hit; 6 B written.
 //   fuse_count_kernel   -- 256 consecutive pixels of ONE view (a chunk never crosses a view, so the pose stays uniform
 //     and the workgroups are in ascending `src` order): the emit flag (with dedupe: the projections into the views
-//     s < r again, and keep of the pixel hit) and, from one ballot per wavefront, the workgroup's number of flags.
+//     s < r again, and keep of the pixel hit) and the workgroup's number of flags (wg_flags_before).
 //     Per pixel: 1 B read + 1 B written; with dedupe, for a kept pixel, 4 + 12 B and per earlier view 5 + 12 + 1 B.
-//   fuse_scan_kernel    -- (ctd_scan.h, shared with tsdf.hip) ONE workgroup: exclusive scan of the workgroup counts,
-//     1024 at a time with a carry, then the per-track totals as differences of the scanned offsets.
-//   fuse_scatter_kernel -- the chunks again: offset of the workgroup + flags before the lane (ballot), and for a flagged
+//   fuse_scan_kernel    -- (ctd_compact.h) ONE workgroup: exclusive scan of the workgroup counts, 1024 at a time with
+//     a carry, then the per-track totals as differences of the scanned offsets.
+//   fuse_scatter_kernel -- the chunks again: offset of the workgroup + flags before the thread, and for a flagged
 //     pixel the world point and its flat index.  Per pixel 1 B read; per point 4 + 12 B read, 12 + 8 B written.
 // Three launches behind the consistency pass, no flag that another workgroup waits on, no atomics: the same bits on every run.
 #include "ctd_common.h"
-#include "ctd_scan.h"
+#include "ctd_compact.h"
 #include "ctd_validate.h"
 #include "ctd_view.h"
 
 namespace ctd {
 namespace {
-
-constexpr int kChunk = 256;                                   // pixels per workgroup of the count and scatter kernels
 
 struct FuseTol {
   float max_px2, max_rel;                                     // max_px * max_px (one f32 product), max_rel
@@ -87,53 +85,37 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(
   fused[g] = k ? acc / (float)(1 + n) : __builtin_nanf("");
 }
 
-// the chunk of a workgroup: pixel p of view r of track b (p >= plane: past the end of the view)
-struct Chunk {
-  int b, r;
-  long p, g;
-};
-__device__ inline Chunk chunk_of_block(int V, long plane, int chunks) {
-  Chunk c;
-  const int bv = blockIdx.x / chunks;
-  c.b = bv / V;
-  c.r = bv % V;
-  c.p = (long)(blockIdx.x % chunks) * kChunk + threadIdx.x;
-  c.g = (long)bv * plane + c.p;
-  return c;
-}
-
 __global__ __launch_bounds__(kChunk) void fuse_count_kernel(
     const float* __restrict__ depth, const uint8_t* __restrict__ valid, const float* __restrict__ ray,
     const float* __restrict__ K, const float* __restrict__ R, const float* __restrict__ t,
     const uint8_t* __restrict__ keep, uint8_t* __restrict__ emit, int* __restrict__ wg_count, int V, int H, int W,
     int chunks, FuseTol tol, int dedupe) {
   __shared__ int wave_n[kChunk / 64];
-  const long plane = (long)H * W;
-  const Chunk c = chunk_of_block(V, plane, chunks);
+  const ChunkItem c = chunk_item(chunks);                     // pixel c.p of the view c.group = view r of track b
+  const int b = c.group / V, r = c.group % V;
+  const long plane = (long)H * W, g = (long)c.group * plane + c.p;
   bool e = false;
   if (c.p < plane) {
-    e = keep[c.g] != 0;
-    if (e && dedupe && c.r > 0) {                             // first view wins: an earlier view that confirms and keeps it
-      const long track = (long)c.b * V * plane;
+    e = keep[g] != 0;
+    if (e && dedupe && r > 0) {                               // first view wins: an earlier view that confirms and keeps it
+      const long track = (long)b * V * plane;
       const float* dt = depth + track;
       const uint8_t* vt = valid ? valid + track : nullptr;
-      const float d_r = dt[c.g - track];
+      const float d_r = dt[g - track];
       const int x = (int)(c.p % W), y = (int)(c.p / W);
-      for (int s = 0; s < c.r; ++s) {
+      for (int s = 0; s < r; ++s) {
         long q;
         float z;
-        if (e && view_match(dt, vt, ray, K, R + (long)c.b * V * 9, t + (long)c.b * V * 3, c.r, s, H, W, x, y, d_r, tol,
-                            q, z) &&
+        if (e && view_match(dt, vt, ray, K, R + (long)b * V * 9, t + (long)b * V * 3, r, s, H, W, x, y, d_r, tol, q, z) &&
             keep[track + s * plane + q])
           e = false;
       }
     }
-    emit[c.g] = e ? 1 : 0;
+    emit[g] = e ? 1 : 0;
   }
-  const int n = __popcll(__ballot(e));
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) wg_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+  int total;
+  (void)wg_flags_before<kChunk>(e, wave_n, total);
+  if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kChunk) void fuse_scatter_kernel(
@@ -141,52 +123,39 @@ __global__ __launch_bounds__(kChunk) void fuse_scatter_kernel(
     const float* __restrict__ R, const float* __restrict__ t, const int* __restrict__ offsets, float* __restrict__ points,
     int64_t* __restrict__ src, int V, int H, int W, int chunks) {
   __shared__ int wave_n[kChunk / 64];
-  const long plane = (long)H * W;
-  const Chunk c = chunk_of_block(V, plane, chunks);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool e = c.p < plane && emit[c.g] != 0;
-  const unsigned long long bits = __ballot(e);
-  if (lane == 0) wave_n[wave] = __popcll(bits);
-  __syncthreads();
+  const ChunkItem c = chunk_item(chunks);                     // pixel c.p of the view c.group
+  const long plane = (long)H * W, g = (long)c.group * plane + c.p;
+  const bool e = c.p < plane && emit[g] != 0;
+  int total;
+  const long o = (long)offsets[blockIdx.x] + wg_flags_before<kChunk>(e, wave_n, total);
   if (!e) return;
-  long o = offsets[blockIdx.x] + __popcll(bits & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) o += wave_n[w];
-  const float* Rr = R + ((long)c.b * V + c.r) * 9;
-  const float* tr = t + ((long)c.b * V + c.r) * 3;
-  const float f = fused[c.g];
-  float p[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) p[i] = f * ray[c.p * 3 + i] - tr[i];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) points[o * 3 + j] = p[0] * Rr[0 * 3 + j] + p[1] * Rr[1 * 3 + j] + p[2] * Rr[2 * 3 + j];
-  src[o] = c.g;
+  camera_to_world(ray + c.p * 3, fused[g], R + (long)c.group * 9, t + (long)c.group * 3, points + o * 3);
+  src[o] = g;
 }
 
-inline int chunks_of(int H, int W) { return (int)(((long)H * W + kChunk - 1) / kChunk); }
+inline int plane_chunks(int H, int W) { return (int)chunks_of((long)H * W); }
 
 struct FuseLayout {                                           // byte offsets into the workspace
   size_t keep, fused, emit, offsets, bytes;
 };
 FuseLayout fuse_layout(int B, int V, int H, int W) {
   const size_t n = (size_t)B * V * H * W;
+  WorkspaceCursor c;
   FuseLayout l;
-  l.keep = 0;
-  l.fused = align_up(n, 256);
-  l.emit = l.fused + align_up(4 * n, 256);
-  l.offsets = l.emit + align_up(n, 256);
-  l.bytes = l.offsets + align_up(sizeof(int) * ((size_t)B * V * chunks_of(H, W) + 1), 256);
+  l.keep = c.take(n);
+  l.fused = c.take(4 * n);
+  l.emit = c.take(n);
+  l.offsets = c.take_counts((size_t)B * V * plane_chunks(H, W));
+  l.bytes = c.bytes;
   return l;
 }
 
 }  // namespace
 
 static bool depth_fusion_supported(int B, int V, int H, int W) {
-  // a launch stays below 2^32 threads: at most 2^24 - 1 workgroups of 256, for the tiles and for the chunks
-  const double views = (double)B * V;
-  return views * ceil_div(W, 64) * ceil_div(H, 4) < 16777216.0 && views * chunks_of(H, W) < 16777216.0;
+  const double views = (double)B * V;                         // the tiles of the consistency pass, the chunks of the fusion
+  return launch_ok(views * tiles_64x4(H, W)) && launch_ok(views * plane_chunks(H, W));
 }
-
-static size_t depth_fuse_workspace_bytes(int B, int V, int H, int W) { return fuse_layout(B, V, H, W).bytes; }
 
 static int depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K,
                                  const float* R, const float* t, float max_px, float max_rel, int min_views,
@@ -214,7 +183,7 @@ static int depth_fuse_points_f32(const float* depth, const uint8_t* valid, const
                                        W, stream);
   if (st != CTD_OK) return st;
   const FuseTol tol = {max_px * max_px, max_rel};
-  const int chunks = chunks_of(H, W), blocks = B * V * chunks;
+  const int chunks = plane_chunks(H, W), blocks = B * V * chunks;
   fuse_count_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(depth, valid, ray, K, R, t, keep, emit, offsets,
                                                                          V, H, W, chunks, tol, dedupe);
   CTD_LAUNCH_CHECK();
@@ -233,14 +202,12 @@ using namespace ctd;
 extern "C" {
 
 static bool depth_fusion_sizes_ok(int B, int V, int H, int W) {
-  // H, W <= 2^24: the bounds of the projected pixel are compared in f32, where W - 1 and H - 1 must be exact
-  return B >= 0 && V >= 1 && H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24) &&
-         (double)B * V * H * W < 2147483648.0;
+  // this family answers INVALID_ARG to the sizes track_shape_status() calls UNSUPPORTED, and UNSUPPORTED to V > 64
+  return B >= 0 && V >= 1 && H >= 1 && W >= 1 && !track_shape_unsupported(B, V, H, W);
 }
 
 static bool depth_fusion_params_ok(float max_px, float max_rel, int min_views) {
-  const float big = 3.402823466e38f;                                                          // (a NaN fails >=)
-  return max_px >= 0.f && max_px <= big && max_rel >= 0.f && max_rel <= big && min_views >= 0 && min_views <= 255;
+  return nonneg_finite(max_px) && nonneg_finite(max_rel) && min_views >= 0 && min_views <= 255;
 }
 
 int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
@@ -262,7 +229,7 @@ int ctd_depth_consistency_f32(const float* depth, const uint8_t* valid, const fl
 
 size_t ctd_depth_fuse_workspace_bytes(int B, int V, int H, int W) {
   if (B <= 0 || V > 64 || !depth_fusion_sizes_ok(B, V, H, W) || !depth_fusion_supported(B, V, H, W)) return 0;
-  return depth_fuse_workspace_bytes(B, V, H, W);
+  return fuse_layout(B, V, H, W).bytes;
 }
 
 int ctd_depth_fuse_points_f32(const float* depth, const uint8_t* valid, const float* ray, const float* K, const float* R,
@@ -279,7 +246,7 @@ int ctd_depth_fuse_points_f32(const float* depth, const uint8_t* valid, const fl
                     {t, 12 * views}};
   if (spans_overlap(s, 7, 13)) return CTD_ERR_INVALID_ARG;
   if (B == 0) return CTD_OK;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return depth_fuse_points_f32(depth, valid, ray, K, R, t, max_px, max_rel, min_views, dedupe, points, src, n_per_track,

@@ -1,9 +1,9 @@
 // depth_icp.hip -- depth-map normals and projective point-to-plane ICP of a track's views (ctd_depth_normals_f32,
 // ctd_depth_icp_system_f32, ctd_depth_icp_update_f32; the rules are stated word for word in include/ctd_hip_icp.h).
 //
-// live_at() and view_transform_point() are those of ctd_view.h, shared with depth_fusion.hip and depth_warp.hip; every
-// f32 product and sum is in the association of the header and the build never contracts them.  Poses and K are indexed
-// by block-uniform values only (track, view, target): scalar loads.
+// live_at() and view_transform_point() are those of ctd_view.h; every f32 product and sum is in the association of the
+// header and the build never contracts them.  Poses and K are indexed by block-uniform values only (track, view,
+// target): scalar loads.
 //   depth_normals_kernel -- a 64 x 4 tile of one view, thread = pixel: the pixel and its four axis neighbours (5 B depth +
 //     valid and 12 B ray each, of which the caches serve the four neighbours), 12 B written.
 //   icp_system_kernel    -- 1024 consecutive pixels of ONE view (a chunk never crosses a view): thread i takes the pixels
@@ -364,13 +364,6 @@ static int depth_icp_update_f32(const double* system, const float* R, const floa
   return CTD_OK;
 }
 
-// 0 ok, else the status of the first failing shape check of the header's lists
-static int icp_shape_status(int B, int V, int H, int W) {
-  if (V < 1 || H < 1 || W < 1 || B < 0 || V > 64) return CTD_ERR_INVALID_ARG;
-  if (H > (1 << 24) || W > (1 << 24) || (double)B * V * H * W >= 2147483648.0) return CTD_ERR_UNSUPPORTED;
-  return CTD_OK;
-}
-
 }  // namespace ctd
 
 using namespace ctd;
@@ -380,9 +373,9 @@ extern "C" {
 int ctd_depth_normals_f32(const float* depth, const uint8_t* valid, const float* ray, float max_rel, float* normal, int B,
                           int V, int H, int W, int device, void* stream) {
   if (!(max_rel >= 0.f) || !depth || !ray || !normal) return CTD_ERR_INVALID_ARG;
-  const int st = icp_shape_status(B, V, H, W);                 // the sizes: INVALID_ARG, then UNSUPPORTED
+  const int st = track_shape_status(B, V, H, W);                 // the sizes: INVALID_ARG, then UNSUPPORTED
   if (st != CTD_OK) return st;
-  if ((double)B * V * (double)(((long)H + 3) / 4) * (double)(((long)W + 63) / 64) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)B * V * tiles_64x4(H, W))) return CTD_ERR_UNSUPPORTED;
   const size_t n = (size_t)B * V * H * W;
   const Span s[] = {{normal, 12 * n}, {depth, 4 * n}, {valid, n}, {ray, 12 * (size_t)H * W}};
   if (spans_overlap(s, 1, 4)) return CTD_ERR_INVALID_ARG;
@@ -393,9 +386,9 @@ int ctd_depth_normals_f32(const float* depth, const uint8_t* valid, const float*
 }
 
 static int icp_system_shape_status(int B, int V, int H, int W) {
-  const int st = icp_shape_status(B, V, H, W);
+  const int st = track_shape_status(B, V, H, W);
   if (st != CTD_OK) return st;
-  if ((double)B * V * (double)icp_chunks(H, W) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)B * V * (double)icp_chunks(H, W))) return CTD_ERR_UNSUPPORTED;
   return CTD_OK;
 }
 
@@ -418,7 +411,7 @@ int ctd_depth_icp_system_f32(const float* depth, const uint8_t* valid, const flo
                        {t, 12 * views}, {target, 4 * views}};
   if (spans_overlap(s, 4, 12)) return CTD_ERR_INVALID_ARG;
   if (B == 0) return CTD_OK;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return depth_icp_system_f32(depth, valid, normal, ray, K, R, t, target, max_dist, system, residual, assoc, B, V, H, W,

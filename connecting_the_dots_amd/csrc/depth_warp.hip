@@ -21,6 +21,7 @@
 // the halo's share), 8 B written.  No atomics.
 #include "../../include/ctd_hip_warp.h"
 #include "ctd_common.h"
+#include "ctd_validate.h"
 #include "ctd_view.h"
 
 namespace ctd {
@@ -183,10 +184,10 @@ static int disparity_band_window_f32(const float* prior, float radius, int D, in
 
 // 0 ok, else the status of the first failing check of the header's list (the pointers excepted)
 static int depth_warp_shape_status(int B, int V, int H, int W) {
-  if (V < 1 || H < 1 || W < 1 || B < 0 || V > 64) return CTD_ERR_INVALID_ARG;
+  if (track_shape_invalid(B, V, H, W)) return CTD_ERR_INVALID_ARG;
   const double plane = (double)H * W;
   if (V * plane >= 4294967296.0 || B * (V * plane) >= 2147483648.0) return CTD_ERR_UNSUPPORTED;
-  if ((double)B * V * (double)warp_chunks(H, W) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)B * V * (double)warp_chunks(H, W))) return CTD_ERR_UNSUPPORTED;
   return CTD_OK;
 }
 
@@ -205,13 +206,12 @@ int ctd_depth_warp_f32(const float* depth, const uint8_t* valid, const float* ra
                        const float* t, const uint8_t* sources, const uint8_t* targets, int splat, float* z,
                        int64_t* src, int B, int V, int H, int W, void* workspace, size_t workspace_bytes, int device,
                        void* stream) {
-  if (splat < 0 || splat > 2 || V < 1 || H < 1 || W < 1 || B < 0 || V > 64) return CTD_ERR_INVALID_ARG;
+  if (splat < 0 || splat > 2 || track_shape_invalid(B, V, H, W)) return CTD_ERR_INVALID_ARG;
   if (!depth || !ray || !K || !R || !t || !z) return CTD_ERR_INVALID_ARG;
   const int st = depth_warp_shape_status(B, V, H, W);
   if (st != CTD_OK) return st;
   if (B == 0) return CTD_OK;
-  if (!workspace || ((uintptr_t)workspace & 255) || workspace_bytes < ctd_depth_warp_workspace_bytes(B, V, H, W))
-    return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, ctd_depth_warp_workspace_bytes(B, V, H, W))) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return depth_warp_f32(depth, valid, ray, K, R, t, sources, targets, splat, z, src, B, V, H, W, workspace,
@@ -224,9 +224,8 @@ int ctd_disparity_band_window_f32(const float* prior, float radius, int D, int w
       N < 0)
     return CTD_ERR_INVALID_ARG;
   if (!prior || !lo || !hi) return CTD_ERR_INVALID_ARG;
-  if ((double)N * H * W >= 2147483648.0 ||
-      (double)N * (double)(((long)H + kBwTH - 1) / kBwTH) * (double)(((long)W + kBwTW - 1) / kBwTW) >= 16777216.0)
-    return CTD_ERR_UNSUPPORTED;
+  static_assert(kBwTW == 64 && kBwTH == 4, "the tile of band_window_kernel is the one tiles_64x4() counts");
+  if ((double)N * H * W >= 2147483648.0 || !launch_ok((double)N * tiles_64x4(H, W))) return CTD_ERR_UNSUPPORTED;
   if (N == 0) return CTD_OK;
   DeviceGuard g(device);
   if (g.status) return g.status;

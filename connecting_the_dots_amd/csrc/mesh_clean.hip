@@ -3,7 +3,8 @@
 //
 // The union-find is that of ctd_union_find.h (shared with disp_filter.hip): parent[] over the vertices, every write an
 // integer atomic min, so the root of a set is its smallest vertex -- the component's label -- whatever order the atomics
-// landed in.  fuse_scan_kernel is that of ctd_scan.h, with B = 1.  A workgroup takes 256 consecutive faces or vertices.
+// landed in.  The workgroup prefix and fuse_scan_kernel (with B = 1) are those of ctd_compact.h.  A workgroup takes 256
+// consecutive faces or vertices.
 //   mc_init_kernel    -- thread = vertex: parent = itself, size counter and kept flag 0; the call's counters 0.  9 B written.
 //   mc_union_kernel   -- thread = face: the validity test (indices, then positions where asked: 12 B + 3 x 12 B gathered),
 //     v0 or -1 to root[] (4 B), and for a valid face the unions (v0,v1), (v0,v2).
@@ -24,31 +25,14 @@
 // Atomics are integer min / add / max; no flag that another workgroup waits on: the same bits on every run.
 #include "../../include/ctd_hip_mesh_clean.h"
 #include "ctd_common.h"
-#include "ctd_scan.h"
+#include "ctd_compact.h"
 #include "ctd_union_find.h"
 #include "ctd_validate.h"
 
 namespace ctd {
 namespace {
 
-constexpr int kChunk = 256;
 typedef unsigned long long u64;
-
-// the number of set flags of the threads before this one in the workgroup, and the workgroup's total (every thread calls)
-__device__ inline int wg_flags_before(bool flag, int* wave_cnt, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const u64 bits = __ballot(flag);
-  if (lane == 0) wave_cnt[wave] = __popcll(bits);
-  __syncthreads();
-  int before = __popcll(bits & ((1ull << lane) - 1ull));
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kChunk / 64; ++w) {
-    before += w < wave ? wave_cnt[w] : 0;
-    total += wave_cnt[w];
-  }
-  return before;
-}
 
 __global__ __launch_bounds__(kChunk) void mc_init_kernel(int* __restrict__ parent, int* __restrict__ count,
                                                          uint8_t* __restrict__ vkeep, u64* __restrict__ best,
@@ -156,7 +140,7 @@ __global__ __launch_bounds__(kChunk) void mc_flag_kernel(const int32_t* __restri
     }
   }
   int total;
-  (void)wg_flags_before(keep, wave_cnt, total);
+  (void)wg_flags_before<kChunk>(keep, wave_cnt, total);
   if (threadIdx.x == 0) {
     wg_faces[blockIdx.x] = total;
     if (keep_largest && blockIdx.x == 0) *n_comp_kept = top_size >= min_faces && top_size > 0 ? 1 : 0;
@@ -168,7 +152,7 @@ __global__ __launch_bounds__(kChunk) void mc_vert_count_kernel(const uint8_t* __
   __shared__ int wave_cnt[kChunk / 64];
   const long v = (long)blockIdx.x * kChunk + threadIdx.x;
   int total;
-  (void)wg_flags_before(v < n_verts && vkeep[v], wave_cnt, total);
+  (void)wg_flags_before<kChunk>(v < n_verts && vkeep[v], wave_cnt, total);
   if (threadIdx.x == 0) wg_verts[blockIdx.x] = total;
 }
 
@@ -180,7 +164,7 @@ __global__ __launch_bounds__(kChunk) void mc_vert_scatter_kernel(const uint8_t* 
   const long v = (long)blockIdx.x * kChunk + threadIdx.x;
   const bool keep = v < n_verts && vkeep[v];
   int total;
-  const int o = vert_offsets[blockIdx.x] + wg_flags_before(keep, wave_cnt, total);
+  const int o = vert_offsets[blockIdx.x] + wg_flags_before<kChunk>(keep, wave_cnt, total);
   if (v < n_verts) vnew[v] = keep ? o : -1;
   if (keep && vert_index && o < cap_verts) vert_index[o] = (int32_t)v;
 }
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(kChunk) void mc_face_scatter_kernel(const int32_t* 
   const long f = (long)blockIdx.x * kChunk + threadIdx.x;
   const bool keep = f < n_faces && fkeep[f];
   int total;
-  const long o = (long)first + wg_flags_before(keep, wave_cnt, total);
+  const long o = (long)first + wg_flags_before<kChunk>(keep, wave_cnt, total);
   if (!keep || o >= cap_faces) return;
   if (faces_out) {
     faces_out[3 * o] = vnew[faces[3 * f]];
@@ -208,24 +192,23 @@ __global__ __launch_bounds__(kChunk) void mc_face_scatter_kernel(const int32_t* 
   if (face_index) face_index[o] = (int32_t)f;
 }
 
-inline size_t chunks_of(int64_t n) { return (size_t)((n + kChunk - 1) / kChunk); }
-
 struct CleanLayout {                                          // byte offsets into the workspace
   size_t parent, count, vnew, root, vkeep, fkeep, face_offsets, vert_offsets, best, bytes;
 };
 CleanLayout clean_layout(int64_t n_verts, int64_t n_faces) {
   const size_t n = (size_t)n_verts, m = (size_t)n_faces;
+  WorkspaceCursor c;
   CleanLayout l;
-  l.parent = 0;
-  l.count = l.parent + align_up(sizeof(int) * n, 256);
-  l.vnew = l.count + align_up(sizeof(int) * n, 256);
-  l.root = l.vnew + align_up(sizeof(int) * n, 256);
-  l.vkeep = l.root + align_up(sizeof(int) * m, 256);
-  l.fkeep = l.vkeep + align_up(n, 256);
-  l.face_offsets = l.fkeep + align_up(m, 256);
-  l.vert_offsets = l.face_offsets + align_up(sizeof(int) * (chunks_of(n_faces) + 1), 256);
-  l.best = l.vert_offsets + align_up(sizeof(int) * (chunks_of(n_verts) + 1), 256);
-  l.bytes = l.best + 256;
+  l.parent = c.take(sizeof(int) * n);
+  l.count = c.take(sizeof(int) * n);
+  l.vnew = c.take(sizeof(int) * n);
+  l.root = c.take(sizeof(int) * m);
+  l.vkeep = c.take(n);
+  l.fkeep = c.take(m);
+  l.face_offsets = c.take_counts((size_t)chunks_of(n_faces));
+  l.vert_offsets = c.take_counts((size_t)chunks_of(n_verts));
+  l.best = c.take(sizeof(u64));
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -233,7 +216,7 @@ CleanLayout clean_layout(int64_t n_verts, int64_t n_faces) {
 int clean_size_status(int64_t n_verts, int64_t n_faces) {
   if (n_verts < 0 || n_faces < 0) return CTD_ERR_INVALID_ARG;
   if (n_faces > (2147483647l) / 3 || n_verts > 2147483647l) return CTD_ERR_UNSUPPORTED;   // 3 * n_faces, n_verts < 2^31
-  if (chunks_of(n_faces) >= (1u << 24) || chunks_of(n_verts) >= (1u << 24)) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)chunks_of(n_faces)) || !launch_ok((double)chunks_of(n_verts))) return CTD_ERR_UNSUPPORTED;
   return CTD_OK;
 }
 
@@ -346,7 +329,7 @@ int ctd_mesh_components_i32(const int32_t* faces, const float* verts, int64_t n_
   const Span s[] = {{label, 4 * m}, {size, 4 * m}, {n_components, 8}, {workspace, need}, {faces, 12 * m},
                     {drop_degenerate ? verts : nullptr, 12 * n}};
   if (spans_overlap(s, 4, 6)) return CTD_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return mesh_components_i32(faces, verts, (long)n_verts, (long)n_faces, drop_degenerate ? 1 : 0, label, size, n_components,
@@ -369,7 +352,7 @@ int ctd_mesh_clean_i32(const int32_t* faces, const float* verts, int64_t n_verts
   const Span s[] = {{faces_out, 12 * cf}, {face_index, 4 * cf}, {vert_index, 4 * cv}, {counts, 32}, {workspace, need},
                     {faces, 12 * m}, {drop_degenerate ? verts : nullptr, 12 * n}};
   if (spans_overlap(s, 5, 7)) return CTD_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return mesh_clean_i32(faces, verts, (long)n_verts, (long)n_faces, drop_degenerate ? 1 : 0, min_faces, keep_largest ? 1 : 0,

@@ -2,20 +2,20 @@
 // (ctd_tsdf_integrate_f32, ctd_tsdf_surface_points_f32, ctd_tsdf_raycast_f32; the rules are stated word for word in
 // include/ctd_hip_tsdf.h).
 //
-// live_at() is that of ctd_view.h, fuse_scan_kernel that of ctd_scan.h (shared with depth_fusion.hip), the chunking, the
-// usability rule and surf_count_kernel those of ctd_tsdf_surf.h (shared with tsdf_mesh.hip); every f32 product
-// and sum is in the association of the header and the build never contracts them.  Poses, K and origin are indexed by
-// block-uniform values only (track, view, loop counter): scalar loads.
+// live_at() and camera_to_world() are those of ctd_view.h, the workgroup prefix and fuse_scan_kernel those of
+// ctd_compact.h, the voxel of a thread, the usability rule and surf_count_kernel those of ctd_tsdf_surf.h (shared with
+// tsdf_mesh.hip); every f32 product and sum is in the association of the header and the build never contracts them.
+// Poses, K and origin are indexed by block-uniform values only (track, view, loop counter): scalar loads.
 //   tsdf_integrate_kernel -- a tile of 64 (x) x 4 (y) voxels of one z slice of one track, thread = voxel, loop over the
 //     views with tsdf and weight in registers.  A row of the tile is 256 contiguous bytes of the volume, and its 64
 //     voxels project onto a short line of neighbouring pixels, four rows onto four such lines: the gather of depth,
 //     valid and ray z of a view stays within a few cache lines per wavefront.  Per voxel 4 B weight read, 4 B tsdf where
 //     the weight is not 0, per view that lands 5 B + 4 B gathered, 8 B written where a view touched the voxel.
 //   surf_count_kernel     -- 256 consecutive voxels of ONE track (a chunk never crosses a track, so the workgroups are
-//     in ascending `src` order): the three crossing flags of a voxel as one byte and, from three ballots per wavefront,
-//     the workgroup's number of points.  Per voxel 8 B read + the +x, +y, +z neighbours (cached rows), 1 B written.
+//     in ascending `src` order): the three crossing flags of a voxel as one byte and the workgroup's number of points
+//     (wg_flags3_before).  Per voxel 8 B read + the +x, +y, +z neighbours (cached rows), 1 B written.
 //   fuse_scan_kernel      -- ONE workgroup: exclusive scan of the workgroup counts, then the per-track totals.
-//   surf_scatter_kernel   -- the chunks again: offset of the workgroup + flags before the lane (ballots), and for each
+//   surf_scatter_kernel   -- the chunks again: offset of the workgroup + flags before the thread, and for each
 //     flag the point, its src and, when asked for, the central-difference normal.  Per voxel 1 B read; per point 16 B read
 //     (+ 48 B for a normal), 12 + 8 (+ 12) B written.
 //   tsdf_raycast_kernel   -- a 64 x 4 tile of one view, thread = pixel: the march along the ray, eight weights and, where
@@ -23,7 +23,7 @@
 // No atomics, no flag that another workgroup waits on: the same bits on every run.
 #include "../../include/ctd_hip_tsdf.h"
 #include "ctd_common.h"
-#include "ctd_scan.h"
+#include "ctd_compact.h"
 #include "ctd_tsdf_surf.h"
 #include "ctd_validate.h"
 #include "ctd_view.h"
@@ -43,6 +43,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(
   const long g = ((long)bk * gr.ny + j) * gr.nx + i, plane = (long)H * W;
   const float* ob = origin + (long)b * 3;
   const float X0 = ob[0] + voxel * (float)i, X1 = ob[1] + voxel * (float)j, X2 = ob[2] + voxel * (float)k;
+  // world_to_camera() and project() of ctd_view.h, written out: through the calls the compiler schedules this loop otherwise
   float w = weight[g];
   float T = w == 0.f ? 0.f : tsdf[g];                          // tsdf is never read where weight == 0
   bool touched = false;
@@ -75,21 +76,16 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSurfChunk) void surf_scatter_kernel(
+__global__ __launch_bounds__(kChunk) void surf_scatter_kernel(
     const float* __restrict__ tsdf, const float* __restrict__ weight, const float* __restrict__ origin, float voxel,
     float min_weight, const uint8_t* __restrict__ emit, const int* __restrict__ offsets, float* __restrict__ points,
     float* __restrict__ normals, int64_t* __restrict__ src, long capacity, Grid gr, long nvox, int chunks) {
-  __shared__ int wave_n[kSurfChunk / 64];
+  __shared__ int wave_n[kChunk / 64];
   const SurfVoxel s = surf_voxel_of_block(gr, nvox, chunks);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int f = s.p < nvox ? emit[s.g] : 0;
-  const unsigned long long b0 = __ballot(f & 1), b1 = __ballot(f & 2), b2 = __ballot(f & 4);
-  if (lane == 0) wave_n[wave] = __popcll(b0) + __popcll(b1) + __popcll(b2);
-  __syncthreads();
+  int total;
+  long o = (long)offsets[blockIdx.x] + wg_flags3_before<kChunk>(f, wave_n, total);
   if (!f) return;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  long o = offsets[blockIdx.x] + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);
-  for (int w = 0; w < wave; ++w) o += wave_n[w];
   const float* ob = origin + (long)s.b * 3;
   const int idx[3] = {s.i, s.j, s.k}, dim[3] = {gr.nx, gr.ny, gr.nz};
   const long stride[3] = {1, gr.nx, (long)gr.nx * gr.ny};
@@ -151,18 +147,16 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restri
   const float* tv = t + bv * 3;
   const float* ob = origin + (long)b * 3;
   const long sy = gr.nx, sz = (long)gr.nx * gr.ny, vol = (long)b * gr.nz * sz;
-  const float r0 = ray[p * 3 + 0], r1 = ray[p * 3 + 1], r2 = ray[p * 3 + 2];
+  const float r[3] = {ray[p * 3 + 0], ray[p * 3 + 1], ray[p * 3 + 2]};
   const float hx = (float)(gr.nx - 2), hy = (float)(gr.ny - 2), hz = (float)(gr.nz - 2);
   float out = __builtin_nanf("");
   bool prev_def = false;
   float prev_T = 0.f;
   for (int n = 0; n < n_steps; ++n) {
     const float d = d_min + step * (float)n;
-    const float P0 = d * r0 - tv[0], P1 = d * r1 - tv[1], P2 = d * r2 - tv[2];
-    const float X0 = P0 * Rv[0] + P1 * Rv[3] + P2 * Rv[6];
-    const float X1 = P0 * Rv[1] + P1 * Rv[4] + P2 * Rv[7];
-    const float X2 = P0 * Rv[2] + P1 * Rv[5] + P2 * Rv[8];
-    const float g0 = (X0 - ob[0]) / voxel, g1 = (X1 - ob[1]) / voxel, g2 = (X2 - ob[2]) / voxel;
+    float X[3];
+    camera_to_world(r, d, Rv, tv, X);
+    const float g0 = (X[0] - ob[0]) / voxel, g1 = (X[1] - ob[1]) / voxel, g2 = (X[2] - ob[2]) / voxel;
     const float i0 = floorf(g0), i1 = floorf(g1), i2 = floorf(g2);
     bool def = i0 >= 0.f && i0 <= hx && i1 >= 0.f && i1 <= hy && i2 >= 0.f && i2 <= hz;   // (a NaN fails the compares)
     float T = 0.f;
@@ -197,18 +191,12 @@ struct SurfLayout {                                           // byte offsets in
   size_t emit, offsets, bytes;
 };
 SurfLayout surf_layout(int B, int nx, int ny, int nz) {
+  WorkspaceCursor c;
   SurfLayout l;
-  l.emit = 0;
-  l.offsets = align_up((size_t)B * nx * ny * nz, 256);
-  l.bytes = l.offsets + align_up(sizeof(int) * ((size_t)B * surf_chunks(nx, ny, nz) + 1), 256);
+  l.emit = c.take((size_t)B * nx * ny * nz);
+  l.offsets = c.take_counts((size_t)B * surf_chunks(nx, ny, nz));
+  l.bytes = c.bytes;
   return l;
-}
-
-int image_status(int B, int V, int H, int W, bool invalid_only) {
-  if (V < 1 || H < 1 || W < 1 || V > 64) return CTD_ERR_INVALID_ARG;
-  if (invalid_only) return CTD_OK;
-  if (H > (1 << 24) || W > (1 << 24) || (double)B * V * H * W >= 2147483648.0) return CTD_ERR_UNSUPPORTED;
-  return CTD_OK;
 }
 
 }  // namespace
@@ -234,13 +222,13 @@ static int tsdf_surface_points_f32(const float* tsdf, const float* weight, const
   const Grid gr = {nx, ny, nz};
   const long nvox = (long)nx * ny * nz;
   const int chunks = (int)surf_chunks(nx, ny, nz), blocks = B * chunks;
-  surf_count_kernel<<<dim3((unsigned)blocks), dim3(kSurfChunk), 0, stream>>>(tsdf, weight, min_weight, emit, offsets, gr,
+  surf_count_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(tsdf, weight, min_weight, emit, offsets, gr,
                                                                             nvox, chunks);
   CTD_LAUNCH_CHECK();
   fuse_scan_kernel<<<dim3(1), dim3(kScan), 0, stream>>>(offsets, blocks, chunks, n_per_track, B);
   CTD_LAUNCH_CHECK();
   if (!points || capacity == 0) return CTD_OK;
-  surf_scatter_kernel<<<dim3((unsigned)blocks), dim3(kSurfChunk), 0, stream>>>(
+  surf_scatter_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(
       tsdf, weight, origin, voxel, min_weight, emit, offsets, points, normals, src, (long)capacity, gr, nvox, chunks);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
@@ -267,12 +255,12 @@ int ctd_tsdf_integrate_f32(float* tsdf, float* weight, const float* origin, floa
                            const uint8_t* valid, const float* ray, const float* K, const float* R, const float* t,
                            float trunc, float max_weight, int B, int nx, int ny, int nz, int V, int H, int W, int device,
                            void* stream) {
-  if (grid_status(B, nx, ny, nz, true) != CTD_OK || image_status(B, V, H, W, true) != CTD_OK) return CTD_ERR_INVALID_ARG;
+  if (grid_status(B, nx, ny, nz, true) != CTD_OK || track_shape_invalid(B, V, H, W)) return CTD_ERR_INVALID_ARG;
   if (!positive_finite(voxel) || !positive_finite(trunc) || !(max_weight >= 1.f && max_weight < __builtin_inff()))
     return CTD_ERR_INVALID_ARG;
   if (!tsdf || !weight || !origin || !depth || !ray || !K || !R || !t) return CTD_ERR_INVALID_ARG;
-  if (grid_status(B, nx, ny, nz, false) != CTD_OK || image_status(B, V, H, W, false) != CTD_OK) return CTD_ERR_UNSUPPORTED;
-  if ((double)B * nz * (double)ceil_div(ny, 4) * (double)ceil_div(nx, 64) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (grid_status(B, nx, ny, nz, false) != CTD_OK || track_shape_unsupported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)B * nz * tiles_64x4(ny, nx))) return CTD_ERR_UNSUPPORTED;
   const size_t nv = (size_t)B * nx * ny * nz, n = (size_t)B * V * H * W, views = (size_t)B * V;
   const Span s[] = {{tsdf, 4 * nv}, {weight, 4 * nv}, {origin, 12 * (size_t)B}, {depth, 4 * n}, {valid, n},
                     {ray, 12 * (size_t)H * W}, {K, 36}, {R, 36 * views}, {t, 12 * views}};
@@ -305,7 +293,7 @@ int ctd_tsdf_surface_points_f32(const float* tsdf, const float* weight, const fl
                     {origin, 12 * (size_t)B}};
   if (spans_overlap(s, 5, 8)) return CTD_ERR_INVALID_ARG;
   if (B == 0) return CTD_OK;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return tsdf_surface_points_f32(tsdf, weight, origin, voxel, min_weight, points, normals, src, n_per_track, capacity, B,
@@ -315,14 +303,13 @@ int ctd_tsdf_surface_points_f32(const float* tsdf, const float* weight, const fl
 int ctd_tsdf_raycast_f32(const float* tsdf, const float* weight, const float* origin, float voxel, const float* ray,
                          const float* R, const float* t, float d_min, float step, int n_steps, float min_weight,
                          float* depth, int B, int nx, int ny, int nz, int V, int H, int W, int device, void* stream) {
-  if (grid_status(B, nx, ny, nz, true) != CTD_OK || image_status(B, V, H, W, true) != CTD_OK || n_steps < 1)
+  if (grid_status(B, nx, ny, nz, true) != CTD_OK || track_shape_invalid(B, V, H, W) || n_steps < 1)
     return CTD_ERR_INVALID_ARG;
-  if (!positive_finite(voxel) || !positive_finite(step) || !positive_finite(min_weight) ||
-      !(d_min >= 0.f && d_min < __builtin_inff()))
+  if (!positive_finite(voxel) || !positive_finite(step) || !positive_finite(min_weight) || !nonneg_finite(d_min))
     return CTD_ERR_INVALID_ARG;
   if (!tsdf || !weight || !origin || !ray || !R || !t || !depth) return CTD_ERR_INVALID_ARG;
-  if (grid_status(B, nx, ny, nz, false) != CTD_OK || image_status(B, V, H, W, false) != CTD_OK) return CTD_ERR_UNSUPPORTED;
-  if ((double)B * V * (double)(((long)H + 3) / 4) * (double)(((long)W + 63) / 64) >= 16777216.0) return CTD_ERR_UNSUPPORTED;
+  if (grid_status(B, nx, ny, nz, false) != CTD_OK || track_shape_unsupported(B, V, H, W)) return CTD_ERR_UNSUPPORTED;
+  if (!launch_ok((double)B * V * tiles_64x4(H, W))) return CTD_ERR_UNSUPPORTED;
   const size_t nv = (size_t)B * nx * ny * nz, n = (size_t)B * V * H * W, views = (size_t)B * V;
   const Span s[] = {{depth, 4 * n}, {tsdf, 4 * nv}, {weight, 4 * nv}, {origin, 12 * (size_t)B}, {ray, 12 * (size_t)H * W},
                     {R, 36 * views}, {t, 12 * views}};

@@ -2,15 +2,15 @@
 // ctd_tsdf_surface_points_f32 (ctd_tsdf_mesh_faces_i32, ctd_tsdf_mesh_case; the rule is stated word for word in
 // include/ctd_hip_mesh.h, the table csrc/ctd_mc_table.h is generated from it by tools/make_mc_table.py).
 //
-// The chunking, the usability rule and surf_count_kernel are those of ctd_tsdf_surf.h (shared with tsdf.hip: the faces
-// index what that file emits, so the flags, their counts and their order come from the same code), fuse_scan_kernel that
-// of ctd_scan.h.  A workgroup takes 256 consecutive voxels of ONE track; a thread takes a voxel and the cell whose corner
-// 0 that voxel is.
+// The voxel of a thread, the usability rule and surf_count_kernel are those of ctd_tsdf_surf.h (shared with tsdf.hip:
+// the faces index what that file emits, so the flags, their counts and their order come from the same code), the
+// workgroup prefixes and fuse_scan_kernel those of ctd_compact.h.  A workgroup takes 256 consecutive voxels of ONE
+// track; a thread takes a voxel and the cell whose corner 0 that voxel is.
 //   surf_count_kernel  -- the three crossing flags of a voxel as one byte, the workgroup's number of points.  Per voxel
 //     8 B read + the +x, +y, +z neighbours (cached rows), 1 B written.
 //   fuse_scan_kernel   -- ONE workgroup: exclusive scan of the point counts (the per-track totals go to the workspace).
-//   mesh_case_kernel   -- per voxel the track-local index of its first point (workgroup offset + flags before the lane,
-//     from ballots), stored where the voxel has a flag: nothing else reads it; per cell the case byte from the eight
+//   mesh_case_kernel   -- per voxel the track-local index of its first point (workgroup offset + flags before the
+//     thread), stored where the voxel has a flag: nothing else reads it; per cell the case byte from the eight
 //     corners' usability and signs (0 when not meshed; the corners are read up to the first unusable one) and, from the
 //     table's count column, the workgroup's number of triangles.  Per voxel 1 B flags read, 1 B case written, the eight
 //     corners' weight and tsdf (8 B compulsory, the rest cached rows and slices), and 4 B index written per flagged voxel.
@@ -22,8 +22,8 @@
 // No atomics, no flag that another workgroup waits on: the same bits on every run.
 #include "../../include/ctd_hip_mesh.h"
 #include "ctd_common.h"
+#include "ctd_compact.h"
 #include "ctd_mc_table.h"
-#include "ctd_scan.h"
 #include "ctd_tsdf_surf.h"
 #include "ctd_validate.h"
 
@@ -34,44 +34,18 @@ namespace {
 alignas(16) __device__ const uint8_t kMcTableDevice[256][16] = {CTD_MC_TABLE_ROWS};
 const uint8_t kMcTableHost[256][16] = {CTD_MC_TABLE_ROWS};
 
-// sum of v over the threads before this one in the workgroup (v >= 0), and the workgroup's total
-__device__ inline int wg_exclusive_sum(int v, int* wave_sum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kSurfChunk / 64; ++w) {
-    before += w < wave ? wave_sum[w] : 0;
-    total += wave_sum[w];
-  }
-  return before + incl - v;
-}
-
-__global__ __launch_bounds__(kSurfChunk) void mesh_case_kernel(const float* __restrict__ tsdf,
-                                                               const float* __restrict__ weight, float min_weight,
-                                                               const uint8_t* __restrict__ emit,
-                                                               const int* __restrict__ point_offsets,
-                                                               int* __restrict__ first_point, uint8_t* __restrict__ cases,
-                                                               int* __restrict__ wg_faces, Grid gr, long nvox, int chunks) {
-  __shared__ int wave_points[kSurfChunk / 64];
-  __shared__ int wave_faces[kSurfChunk / 64];
+__global__ __launch_bounds__(kChunk) void mesh_case_kernel(const float* __restrict__ tsdf,
+                                                           const float* __restrict__ weight, float min_weight,
+                                                           const uint8_t* __restrict__ emit,
+                                                           const int* __restrict__ point_offsets,
+                                                           int* __restrict__ first_point, uint8_t* __restrict__ cases,
+                                                           int* __restrict__ wg_faces, Grid gr, long nvox, int chunks) {
+  __shared__ int wave_points[kChunk / 64];
+  __shared__ int wave_faces[kChunk / 64];
   const SurfVoxel s = surf_voxel_of_block(gr, nvox, chunks);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool live = s.p < nvox;
-  // the voxel's first point: the order of surf_scatter_kernel (ascending voxel, then axis)
   const int f = live ? emit[s.g] : 0;
-  const unsigned long long b0 = __ballot(f & 1), b1 = __ballot(f & 2), b2 = __ballot(f & 4);
-  if (lane == 0) wave_points[wave] = __popcll(b0) + __popcll(b1) + __popcll(b2);
-  // the cell's case
-  int cs = 0;
+  int cs = 0;                                                   // the cell's case
   // the cell's position in 32-bit arithmetic (p < nx * ny * nz < 2^31); s.i, s.j, s.k, from 64-bit divisions, stay unused
   const unsigned p32 = (unsigned)s.p, row = p32 / (unsigned)gr.nx;
   const int ci = (int)(p32 - row * (unsigned)gr.nx), ck = (int)(row / (unsigned)gr.ny), cj = (int)(row - (unsigned)ck * (unsigned)gr.ny);
@@ -89,30 +63,26 @@ __global__ __launch_bounds__(kSurfChunk) void mesh_case_kernel(const float* __re
     }
     if (!meshed) cs = 0;
   }
-  int n_faces = kMcTableDevice[cs][15];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) n_faces += __shfl_xor(n_faces, d);
-  if (lane == 0) wave_faces[wave] = n_faces;
-  __syncthreads();
+  // the voxel's first point, in the order of surf_scatter_kernel (ascending voxel, then axis), and the workgroup's faces
+  int n_points, n_faces;
+  const int before = wg_flags3_before<kChunk>(f, wave_points, n_points);
+  (void)wg_exclusive_sum<kChunk>(kMcTableDevice[cs][15], wave_faces, n_faces);
   if (live) {
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int o = point_offsets[blockIdx.x] - point_offsets[(long)s.b * chunks] + __popcll(b0 & below) + __popcll(b1 & below) +
-            __popcll(b2 & below);
-    for (int w = 0; w < wave; ++w) o += wave_points[w];
+    const int o = point_offsets[blockIdx.x] - point_offsets[(long)s.b * chunks] + before;
     if (f) first_point[s.g] = o;                                // read only through a set flag of the voxel
     cases[s.g] = (uint8_t)cs;
   }
-  if (threadIdx.x == 0) wg_faces[blockIdx.x] = wave_faces[0] + wave_faces[1] + wave_faces[2] + wave_faces[3];
+  if (threadIdx.x == 0) wg_faces[blockIdx.x] = n_faces;
 }
 
-__global__ __launch_bounds__(kSurfChunk) void mesh_scatter_kernel(const uint8_t* __restrict__ emit,
-                                                                  const int* __restrict__ first_point,
-                                                                  const uint8_t* __restrict__ cases,
-                                                                  const int* __restrict__ face_offsets,
-                                                                  int32_t* __restrict__ faces, long capacity, Grid gr,
-                                                                  long nvox, int chunks) {
+__global__ __launch_bounds__(kChunk) void mesh_scatter_kernel(const uint8_t* __restrict__ emit,
+                                                              const int* __restrict__ first_point,
+                                                              const uint8_t* __restrict__ cases,
+                                                              const int* __restrict__ face_offsets,
+                                                              int32_t* __restrict__ faces, long capacity, Grid gr,
+                                                              long nvox, int chunks) {
   __shared__ uint4 table[256];                                // kMcTableDevice, a row per thread
-  __shared__ int wave_sum[kSurfChunk / 64];
+  __shared__ int wave_sum[kChunk / 64];
   // a workgroup without faces, or with all of them past the capacity, has nothing to write (uniform: before any barrier)
   const int first = face_offsets[blockIdx.x];
   if (face_offsets[blockIdx.x + 1] == first || first >= capacity) return;
@@ -123,7 +93,7 @@ __global__ __launch_bounds__(kSurfChunk) void mesh_scatter_kernel(const uint8_t*
   const uint8_t* row = reinterpret_cast<const uint8_t*>(&table[cs]);
   const int n = row[15];
   int total;
-  long o = (long)first + wg_exclusive_sum(n, wave_sum, total);
+  long o = (long)first + wg_exclusive_sum<kChunk>(n, wave_sum, total);
   if (n == 0) return;                                         // (cs != 0 only at a cell inside the grid)
   const long stride[3] = {1, gr.nx, (long)gr.nx * gr.ny};
   for (int t = 0; t < n; ++t, ++o) {
@@ -143,15 +113,16 @@ struct MeshLayout {                                           // byte offsets in
   size_t emit, point_offsets, first_point, cases, face_offsets, n_points, bytes;
 };
 MeshLayout mesh_layout(int B, int nx, int ny, int nz) {
-  const size_t nv = (size_t)B * nx * ny * nz, counts = align_up(sizeof(int) * ((size_t)B * surf_chunks(nx, ny, nz) + 1), 256);
+  const size_t nv = (size_t)B * nx * ny * nz, wgs = (size_t)B * surf_chunks(nx, ny, nz);
+  WorkspaceCursor c;
   MeshLayout l;
-  l.emit = 0;
-  l.point_offsets = align_up(nv, 256);
-  l.first_point = l.point_offsets + counts;
-  l.cases = l.first_point + align_up(sizeof(int) * nv, 256);
-  l.face_offsets = l.cases + align_up(nv, 256);
-  l.n_points = l.face_offsets + counts;
-  l.bytes = l.n_points + align_up(sizeof(int64_t) * (size_t)B, 256);
+  l.emit = c.take(nv);
+  l.point_offsets = c.take_counts(wgs);
+  l.first_point = c.take(sizeof(int) * nv);
+  l.cases = c.take(nv);
+  l.face_offsets = c.take_counts(wgs);
+  l.n_points = c.take(sizeof(int64_t) * (size_t)B);
+  l.bytes = c.bytes;
   return l;
 }
 
@@ -178,18 +149,18 @@ static int tsdf_mesh_faces_i32(const float* tsdf, const float* weight, float min
   const Grid gr = {nx, ny, nz};
   const long nvox = (long)nx * ny * nz;
   const int chunks = (int)surf_chunks(nx, ny, nz), blocks = B * chunks;
-  surf_count_kernel<<<dim3((unsigned)blocks), dim3(kSurfChunk), 0, stream>>>(tsdf, weight, min_weight, emit, point_offsets,
+  surf_count_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(tsdf, weight, min_weight, emit, point_offsets,
                                                                             gr, nvox, chunks);
   CTD_LAUNCH_CHECK();
   fuse_scan_kernel<<<dim3(1), dim3(kScan), 0, stream>>>(point_offsets, blocks, chunks, n_points, B);
   CTD_LAUNCH_CHECK();
-  mesh_case_kernel<<<dim3((unsigned)blocks), dim3(kSurfChunk), 0, stream>>>(tsdf, weight, min_weight, emit, point_offsets,
+  mesh_case_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(tsdf, weight, min_weight, emit, point_offsets,
                                                                            first_point, cases, face_offsets, gr, nvox, chunks);
   CTD_LAUNCH_CHECK();
   fuse_scan_kernel<<<dim3(1), dim3(kScan), 0, stream>>>(face_offsets, blocks, chunks, n_faces_per_track, B);
   CTD_LAUNCH_CHECK();
   if (!faces || capacity == 0) return CTD_OK;
-  mesh_scatter_kernel<<<dim3((unsigned)blocks), dim3(kSurfChunk), 0, stream>>>(emit, first_point, cases, face_offsets, faces,
+  mesh_scatter_kernel<<<dim3((unsigned)blocks), dim3(kChunk), 0, stream>>>(emit, first_point, cases, face_offsets, faces,
                                                                               (long)capacity, gr, nvox, chunks);
   CTD_LAUNCH_CHECK();
   return CTD_OK;
@@ -219,7 +190,7 @@ int ctd_tsdf_mesh_faces_i32(const float* tsdf, const float* weight, float min_we
   const Span s[] = {{faces, 12 * cap}, {n_faces_per_track, 8 * (size_t)B}, {workspace, need}, {tsdf, 4 * nv}, {weight, 4 * nv}};
   if (spans_overlap(s, 3, 5)) return CTD_ERR_INVALID_ARG;
   if (B == 0) return CTD_OK;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return CTD_ERR_WORKSPACE;
+  if (!workspace_ok(workspace, workspace_bytes, need)) return CTD_ERR_WORKSPACE;
   DeviceGuard g(device);
   if (g.status) return g.status;
   return tsdf_mesh_faces_i32(tsdf, weight, min_weight, faces, n_faces_per_track, capacity, B, nx, ny, nz, workspace,

@@ -250,8 +250,62 @@ def test_a_long_strip_is_one_component_labelled_0(order):
     assert (comps[0] == 0).all() and (comps[1] == m).all() and comps[2] == 1
 
 
-@pytest.mark.parametrize("k", [255, 256, 257, 1])
+BIG = 256 * 1024                                                 # faces of 1024 workgroups: one full round of the scan
+
+
+def pattern_mesh(m):
+    """m faces in blocks of five, each block over ten vertices of its own: a triangle, a quad of two triangles, a
+    triangle, and a face made invalid by a repeated index -> faces, n_verts and, by index arithmetic on the pattern,
+    label, size and n_components"""
+    f = np.arange(m)
+    p, r = f // 5, f % 5
+    corners = np.array([[0, 1, 2], [3, 4, 5], [3, 5, 6], [7, 8, 9], [7, 7, 8]])
+    faces = (10 * p[:, None] + corners[r]).astype(np.int32)
+    valid = r != 4
+    label = np.where(valid, faces[:, 0], -1).astype(np.int32)     # the first index of a valid face is its block's smallest
+    size = valid.astype(np.int32) + ((r == 1) & (f + 1 < m)) + (r == 2)   # (the last quad may lack its second half)
+    return faces, 10 * ((m + 4) // 5), label, size, int((valid & (r != 2)).sum())
+
+
+def straddled_capacity(flags):
+    """a capacity one short of where the middle workgroup's kept items end: that workgroup writes some of them, not all"""
+    ends = np.cumsum(np.add.reduceat(flags.astype(np.int64), np.arange(0, len(flags), 256)))
+    i = len(ends) // 2
+    assert ends[i] - ends[i - 1] >= 2
+    return int(ends[i]) - 1
+
+
+def check_pattern_mesh(m):
+    """mesh_components and mesh_clean on pattern_mesh(m): more workgroup counts, of faces and of vertices, than one round
+    of the scan takes (or exactly as many faces), a chunk of one face at BIG + 1"""
+    faces, n, label, size, n_comp = pattern_mesh(m)
+    got = components_c_call(faces, None, n, False)
+    assert np.array_equal(got[0], label) and np.array_equal(got[1], size) and got[2] == n_comp, "m = %d: components" % m
+    first_of_component = np.arange(m) % 5 != 2
+    for min_faces in (1, 2):
+        tag = "m = %d min_faces %d" % (m, min_faces)
+        keep = size >= min_faces
+        used = np.zeros(n, bool)
+        used[faces[keep].reshape(-1)] = True
+        want_vi, want_fi = np.nonzero(used)[0].astype(np.int32), np.nonzero(keep)[0].astype(np.int32)
+        want_fo = (np.cumsum(used) - 1)[faces[keep]].astype(np.int32)
+        nv, nf = len(want_vi), len(want_fi)
+        want_counts = [nv, nf, n_comp, int((keep & first_of_component).sum())]
+        assert nf > BIG // 4 and (want_counts[3] < n_comp) == (min_faces == 2)    # the cases are not vacuous
+        # capacities: everything, and (min_faces 1) about half, inside a workgroup's kept items
+        for cf, cv in ((m, n),) + (((straddled_capacity(keep), straddled_capacity(used)),) if min_faces == 1 else ()):
+            fo, fi, vi, counts = clean_c_call(faces, None, n, False, min_faces, False, cf, cv)
+            cf, cv = min(cf, nf), min(cv, nv)
+            assert counts.tolist() == want_counts, "%s: counts %s vs %s" % (tag, counts, want_counts)
+            assert np.array_equal(fo[:cf], want_fo[:cf]) and (fo[cf:] == -7).all(), tag + ": faces_out"
+            assert np.array_equal(fi[:cf], want_fi[:cf]) and (fi[cf:] == -7).all(), tag + ": face_index"
+            assert np.array_equal(vi[:cv], want_vi[:cv]) and (vi[cv:] == -7).all(), tag + ": vert_index"
+
+
+@pytest.mark.parametrize("k", [255, 256, 257, 1, BIG - 1, BIG, BIG + 1])
 def test_sizes_around_the_chunk(k):
+    if k >= BIG - 1:                                               # too many faces for the restatement's union-find
+        return check_pattern_mesh(k)
     rs = np.random.RandomState(k)
     n = k if k > 1 else 3
     first = rs.randint(0, n, k)

@@ -33,6 +33,10 @@ B = 2
 # border; 64 x 5 x 7 fills rows exactly; 2 x 2 x 2 is one cell in less than a wavefront; 5 x 1 x 4 has no cell at all;
 # 3 x 43 x 2 = 258 voxels is one full chunk and a chunk of two voxels
 GRIDS = [(33, 18, 21), (64, 5, 7), (2, 2, 2), (5, 1, 4), (3, 43, 2)]
+# the one-workgroup scan takes 1024 workgroup counts a round, and the grids above give 98 at most.  64^3 is 1024 chunks a
+# track: 2048 counts, two full rounds that meet on the track border; 64 x 64 x 65 is 1040 chunks a track: 2080 counts,
+# three rounds, a round border inside track 1.  257 voxels leave one live thread in the last chunk; 64 x 4 is one chunk
+SCAN_GRIDS = [(64, 64, 64), (64, 64, 65), (257, 1, 1), (64, 4, 1)]
 SENTINEL = 0xA5
 
 MIN_MESH_SHARE = 1 - 2 * 0.00160                                # measured 99.840 % / 99.920 %
@@ -136,10 +140,11 @@ def check_mesh(te, mesh, T, w, min_weight, what):
     return m, set(case[meshed].tolist())
 
 
-@pytest.mark.parametrize("dims", GRIDS)
+@pytest.mark.parametrize("dims", GRIDS + SCAN_GRIDS)
 def test_faces_equal_the_restatement(te, mesh, dims):
     n_faces, cases = 0, set()
-    for seed, min_weight, empty in ((0, 1.0, None), (1, 2.0, None), (2, 1.0, 1), (3, 1.0, 0)):
+    runs = ((0, 1.0, None), (1, 2.0, None), (2, 1.0, 1), (3, 1.0, 0))
+    for seed, min_weight, empty in runs[:1] if dims in SCAN_GRIDS[:2] else runs:    # (one volume of half a million voxels)
         T, w = random_volume(dims, seed, empty_track=empty)
         m, met = check_mesh(te, mesh, T, w, min_weight, "%s seed %d min_weight %g" % (dims, seed, min_weight))
         n_faces += m
@@ -148,7 +153,9 @@ def test_faces_equal_the_restatement(te, mesh, dims):
     if dims == GRIDS[0]:
         assert cases == set(range(256))                             # the restatement met every case, so the kernel did
         assert n_faces > 10000
-    if dims == (5, 1, 4):
+    if dims in SCAN_GRIDS[:2]:
+        assert n_faces > 100000                                     # the cases are not vacuous
+    if dims in ((5, 1, 4), (257, 1, 1), (64, 4, 1)):
         assert n_faces == 0
 
 
