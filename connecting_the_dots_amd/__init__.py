@@ -14,6 +14,8 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
     mesh                 the triangle mesh of a TSDF volume (include/ctd_hip_mesh.h) for renderer.MeshBVH, and PLY files
     meshops              mesh clean-up (include/ctd_hip_mesh_clean.h): connected components, removal of small components,
                          of faces with coincident vertices and of unreferenced vertices, compaction
+    mesheval             nearest-face queries (include/ctd_hip_mesh_dist.h) by brute force or through renderer.MeshBVH, surface
+                         samples, and the accuracy / completeness / Chamfer / F-score of one mesh against another
 """
 from . import torchext  # noqa: F401
 

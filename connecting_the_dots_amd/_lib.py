@@ -1,5 +1,6 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h and ctd_hip_mesh_clean.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h and
+ctd_hip_mesh_dist.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -212,6 +213,12 @@ MESH_CLEAN_SIGNATURES = {
                                     _c_size_t, _c_int, _vp]),
 }
 
+# nearest-face queries of include/ctd_hip_mesh_dist.h (an addition beside the headers above; mesheval.point_mesh_distance,
+# mesheval.reconstruction_error)
+MESH_DIST_SIGNATURES = {
+    "ctd_point_mesh_distance_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -227,7 +234,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
-                                  list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items())):
+                                  list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
+                                  list(MESH_DIST_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

@@ -55,33 +55,16 @@
 //   costs the visits along their path to the root.
 #include <cstdint>
 
+#include "ctd_bvh.h"
 #include "ctd_common.h"
 #include "ctd_render.h"
 
 namespace ctd {
 
-constexpr int kBvhMaxFaces = 1 << 28;
+// the buffer's layout, its view, the header check and the stack depth they share with point_mesh.hip: ctd_bvh.h
 constexpr int kLeafFaces = 4;       // a node over <= kLeafFaces sorted faces is a leaf
-constexpr int kStack = 64;          // per-lane traversal stack (LDS), entries
-constexpr int kMaxDepth = kStack - 2;
-constexpr int kBvhMagic = 0x42445443;   // "CTDB"
 constexpr int kSortThreads = 256, kSortItems = 16, kSortTile = kSortThreads * kSortItems;
 constexpr int kDigitBits = 4, kDigits = 1 << kDigitBits, kKeyBits = 63;
-
-static inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-struct BvhLayout {
-  size_t box, meta, tris, total;
-};
-static BvhLayout bvh_layout(long n) {
-  const long nodes = n > 0 ? 2 * n - 1 : 0;
-  BvhLayout L;
-  L.box = 64;
-  L.meta = L.box + align16((size_t)nodes * 32);
-  L.tris = L.meta + align16((size_t)nodes * 16);
-  L.total = L.tris + align16((size_t)n * 48);
-  return L;
-}
 
 struct WsLayout {
   size_t keys0, keys1, vals0, vals1, hist, counters, bounds, total;
@@ -394,20 +377,6 @@ static int mesh_bvh_build_f32(const float* verts, const int* faces, int n, void*
 
 // ---------------------------------------------------------------------------------------------------- traversal
 
-struct BvhView {
-  const float4* box;
-  const int4* meta;
-  const float4* tris;
-  int n, n_nodes;
-};
-
-static BvhView bvh_view(const void* bvh, int n) {
-  const BvhLayout L = bvh_layout(n);
-  const char* B = (const char*)bvh;
-  return BvhView{(const float4*)(B + L.box), (const int4*)(B + L.meta), (const float4*)(B + L.tris), n,
-                 n > 0 ? 2 * n - 1 : 0};
-}
-
 __device__ inline float lower_rel(float x) { return x > 0 ? x * (1.f - 1e-6f) : x * (1.f + 1e-6f); }
 __device__ inline float upper_rel(float x) { return x > 0 ? x * (1.f + 1e-6f) : x * (1.f - 1e-6f); }
 
@@ -539,17 +508,6 @@ __global__ __launch_bounds__(64) void render_mesh_bvh_kernel(BvhView bv, const f
   const Hit hit = bvh_nearest(bv, stack, orig, dir);
   mesh_shade(verts, colors, normals, faces, hit.valid, hit.face, orig, dir, hit.t, hit.u, hit.v, ka, kd, ks, alpha, depth,
              color, normal, idx);
-}
-
-// reads the tree's header (one small synchronous copy) and refuses a buffer that is not a tree of n faces or is
-// deeper than the traversal stack
-static int bvh_check(const void* bvh, int n, hipStream_t stream) {
-  int header[16];
-  CTD_HIP_TRY(hipMemcpyAsync(header, bvh, sizeof(header), hipMemcpyDeviceToHost, stream));
-  CTD_HIP_TRY(hipStreamSynchronize(stream));
-  if (header[0] != kBvhMagic || header[1] != n) return CTD_ERR_INVALID_ARG;
-  if (header[3] < 0 || header[3] > kMaxDepth) return CTD_ERR_UNSUPPORTED;
-  return CTD_OK;
 }
 
 static int render_mesh_proj_bvh_f32(const void* bvh, const float* verts, const float* colors, const int* faces,
