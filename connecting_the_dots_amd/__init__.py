@@ -16,6 +16,8 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          of faces with coincident vertices and of unreferenced vertices, compaction
     mesheval             nearest-face queries (include/ctd_hip_mesh_dist.h) by brute force or through renderer.MeshBVH, surface
                          samples, and the accuracy / completeness / Chamfer / F-score of one mesh against another
+    meshcolor            colours for mesh points from a track's views (include/ctd_hip_mesh_color.h): projection, occlusion
+                         against the mesh by brute force or through renderer.MeshBVH, bilinear sample, blend of the views
 """
 from . import torchext  # noqa: F401
 

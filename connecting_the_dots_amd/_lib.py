@@ -1,6 +1,6 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h and
-ctd_hip_mesh_dist.h).
+ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h,
+ctd_hip_mesh_dist.h and ctd_hip_mesh_color.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -219,6 +219,14 @@ MESH_DIST_SIGNATURES = {
     "ctd_point_mesh_distance_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
 }
 
+# colours for mesh points from a track's views of include/ctd_hip_mesh_color.h (an addition beside the headers above;
+# meshcolor.view_colors, meshcolor.color_tsdf_mesh)
+MESH_COLOR_SIGNATURES = {
+    "ctd_mesh_view_colors_f32": (_c_int, [_vp, _vp, _c_int] + [_vp] * 5 + [_c_int] * 4 + [_vp, _c_int, _vp, _c_int, _vp,
+                                                                                       _c_float, _c_float, _c_int] +
+                                 [_vp] * 4 + [_c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -235,7 +243,7 @@ def lib():
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
                                   list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
-                                  list(MESH_DIST_SIGNATURES.items())):
+                                  list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args
