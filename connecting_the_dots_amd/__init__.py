@@ -18,6 +18,8 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          samples, and the accuracy / completeness / Chamfer / F-score of one mesh against another
     meshcolor            colours for mesh points from a track's views (include/ctd_hip_mesh_color.h): projection, occlusion
                          against the mesh by brute force or through renderer.MeshBVH, bilinear sample, blend of the views
+    meshsmooth           the mesh's connectivity by vertex (include/ctd_hip_mesh_smooth.h): one-rings, incident faces, boundary
+                         and non-manifold edges; Taubin smoothing over the one-rings; area-weighted vertex normals
 """
 from . import torchext  # noqa: F401
 

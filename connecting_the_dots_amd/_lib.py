@@ -1,6 +1,6 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
 ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h,
-ctd_hip_mesh_dist.h and ctd_hip_mesh_color.h).
+ctd_hip_mesh_dist.h, ctd_hip_mesh_color.h and ctd_hip_mesh_smooth.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -227,6 +227,18 @@ MESH_COLOR_SIGNATURES = {
                                  [_vp] * 4 + [_c_int, _vp]),
 }
 
+# connectivity by vertex, Taubin smoothing and vertex normals of include/ctd_hip_mesh_smooth.h (an addition beside the
+# headers above; meshsmooth.MeshAdjacency, meshsmooth.mesh_smooth, meshsmooth.vertex_normals, meshsmooth.smooth_tsdf_mesh)
+MESH_SMOOTH_SIGNATURES = {
+    "ctd_mesh_adjacency_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
+    "ctd_mesh_adjacency_i32": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_size_t, _c_int,
+                                        _vp]),
+    "ctd_mesh_smooth_workspace_bytes": (_c_size_t, [_c_i64]),
+    "ctd_mesh_smooth_f32": (_c_int, [_vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _c_float, _c_float, _c_int, _vp, _vp, _c_size_t,
+                                     _c_int, _vp]),
+    "ctd_mesh_vertex_normals_f32": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -243,7 +255,8 @@ def lib():
                                   list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
                                   list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
-                                  list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())):
+                                  list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()) +
+                                  list(MESH_SMOOTH_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args
