@@ -1,6 +1,7 @@
 // ctd_bvh.h -- the buffer of ctd_mesh_bvh_build_f32 as its readers see it: the layout of its sections, a view of them
-// for kernels, and the header check every traversal makes before it launches.  Shared by the ray casters
-// (render_bvh.hip, which also builds the tree and documents the format) and the nearest-face query (point_mesh.hip).
+// for kernels, and the header check every traversal makes before it launches.  Three files read the buffer: the ray
+// casters (render_bvh.hip, which also builds the tree and documents the format), the nearest-face query (point_mesh.hip)
+// and the view colours' occlusion query (mesh_color.hip); what their traversals share beyond it is in ctd_mesh_query.h.
 #pragma once
 
 #include "ctd_common.h"

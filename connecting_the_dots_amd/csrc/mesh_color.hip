@@ -39,6 +39,7 @@
 #include "ctd_bvh.h"
 #include "ctd_bvh_ray.h"
 #include "ctd_common.h"
+#include "ctd_mesh_query.h"
 #include "ctd_render.h"
 #include "ctd_validate.h"
 #include "ctd_view.h"
@@ -191,22 +192,7 @@ __global__ __launch_bounds__(kColorBruteThreads) void view_colors_brute_kernel(C
     for (int base = 0; base < n_faces; base += kColorBruteThreads) {
       // the previous tile has been read by every lane; a view that no lane has left to decide streams no more
       if (!__syncthreads_or(pending)) break;
-      const int j = base + tid;
-      int valid = 0;
-      if (j < n_faces) {
-        const int i0 = faces[(long)j * 3], i1 = faces[(long)j * 3 + 1], i2 = faces[(long)j * 3 + 2];
-        valid = i0 >= 0 && i0 < n_verts && i1 >= 0 && i1 < n_verts && i2 >= 0 && i2 < n_verts;
-        if (valid) {
-          const float *p = verts + (long)i0 * 3, *q = verts + (long)i1 * 3, *r = verts + (long)i2 * 3;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            tri[tid * 9 + k] = p[k];
-            tri[tid * 9 + 3 + k] = q[k];
-            tri[tid * 9 + 6 + k] = r[k];
-          }
-        }
-      }
-      ok[tid] = valid;
+      face_tile_load<kColorBruteThreads>(tri, ok, base, verts, n_verts, faces, n_faces);
       __syncthreads();
       if (!pending) continue;
       const int cnt = min(kColorBruteThreads, n_faces - base);
@@ -228,30 +214,28 @@ __device__ inline bool bvh_occluded(const BvhView& bv, int* __restrict__ stack, 
   const bool exact = finite3(g.C) && finite3(g.dir) && isfinite(g.t_max);   // otherwise: visit every face
   const float dn = norm3(g.dir) * 1.00001f;
   int sp = 1;
-  stack[0] = 0;
+  lane_at(stack, 0) = 0;
   while (sp > 0) {
-    const int node = stack[(--sp) * 64];
+    const int node = lane_at(stack, --sp);
     if (exact && prune(g.C, g.dir, dn, bv.box[(long)node * 2], bv.box[(long)node * 2 + 1], g.t_max)) continue;
     const int4 m = bv.meta[node];
     if (m.x < 0) {
       const int first = -(m.x + 1);
       for (int k = 0; k < m.y; ++k) {
-        const float4 p = bv.tris[(long)(first + k) * 3], q = bv.tris[(long)(first + k) * 3 + 1],
-                     r = bv.tris[(long)(first + k) * 3 + 2];
-        const float v0[3] = {p.x, p.y, p.z}, v1[3] = {q.x, q.y, q.z}, v2[3] = {r.x, r.y, r.z};
+        float v0[3], v1[3], v2[3];
+        bvh_leaf_tri(bv, first + k, v0, v1, v2);
         if (occludes(g, v0, v1, v2)) return true;
       }
     } else if (sp + 2 <= kStack) {                     // always true for depth <= kMaxDepth (checked at launch)
-      stack[(sp++) * 64] = m.y;
-      stack[(sp++) * 64] = m.x;
+      lane_at(stack, sp++) = m.y;
+      lane_at(stack, sp++) = m.x;
     }
   }
   return false;
 }
 
 __global__ __launch_bounds__(64) void view_colors_bvh_kernel(ColorArgs a, BvhView bv) {
-  __shared__ int stack_lds[kStack * 64];
-  int* stack = stack_lds + threadIdx.x;
+  int* stack = lane_stack();
   const long i = (long)blockIdx.x * 64 + threadIdx.x;
   if (i >= a.n_points) return;
   const float X[3] = {a.points[i * 3], a.points[i * 3 + 1], a.points[i * 3 + 2]};
@@ -265,22 +249,6 @@ __global__ __launch_bounds__(64) void view_colors_bvh_kernel(ColorArgs a, BvhVie
     view_finish(a, i, v, bits, g, blend);
   }
   blend.store(a, i);
-}
-
-static int mesh_view_colors_f32(const ColorArgs& a, const float* verts, int n_verts, const int* faces, int n_faces,
-                                const void* bvh, hipStream_t stream) {
-  if (bvh && n_faces > 0) {
-    const int st = bvh_check(bvh, n_faces, stream);
-    if (st != CTD_OK) return st;
-    hipLaunchKernelGGL(view_colors_bvh_kernel, dim3((unsigned)ceil_div(a.n_points, 64)), dim3(64), 0, stream, a,
-                       bvh_view(bvh, n_faces));
-    CTD_LAUNCH_CHECK();
-    return CTD_OK;
-  }
-  hipLaunchKernelGGL(view_colors_brute_kernel, dim3((unsigned)ceil_div(a.n_points, kColorBruteThreads)),
-                     dim3(kColorBruteThreads), 0, stream, a, verts, n_verts, faces, n_faces);
-  CTD_LAUNCH_CHECK();
-  return CTD_OK;
 }
 
 }  // namespace ctd
@@ -298,8 +266,7 @@ int ctd_mesh_view_colors_f32(const float* points, const float* normals, int n_po
     return CTD_ERR_INVALID_ARG;
   if ((mode != 0 && mode != 1) || !nonneg_finite(margin) || !(min_cos >= 0.f && min_cos < 1.f)) return CTD_ERR_INVALID_ARG;
   if (n_points > 0 && (!points || !images || !K || !R || !t || !color || !weight || !n_views)) return CTD_ERR_INVALID_ARG;
-  if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return CTD_ERR_INVALID_ARG;
-  if (bvh && (uintptr_t)bvh % 16) return CTD_ERR_INVALID_ARG;
+  if (!mesh_group_ok(verts, n_verts, faces, n_faces, bvh)) return CTD_ERR_INVALID_ARG;
   if (H > (1 << 24) || W > (1 << 24) || (double)V * C * H * W >= 2147483648.0 || (double)n_points * 3 >= 2147483648.0 ||
       (double)n_points * V >= 2147483648.0 || n_faces > kBvhMaxFaces)
     return CTD_ERR_UNSUPPORTED;
@@ -324,7 +291,16 @@ int ctd_mesh_view_colors_f32(const float* points, const float* normals, int n_po
   if (g.status) return g.status;
   const ColorArgs a{points, normals, n_points, images, valid, K, R, t, V, C, H, W, margin, min_cos, mode,
                     color, weight, n_views, flags};
-  return mesh_view_colors_f32(a, verts, n_verts, faces, n_faces, bvh, (hipStream_t)stream);
+  const hipStream_t s = (hipStream_t)stream;
+  return tree_or_brute(
+      bvh, n_faces, s,
+      [&](const BvhView& bv) {
+        hipLaunchKernelGGL(view_colors_bvh_kernel, dim3((unsigned)ceil_div(n_points, 64)), dim3(64), 0, s, a, bv);
+      },
+      [&] {
+        hipLaunchKernelGGL(view_colors_brute_kernel, dim3((unsigned)ceil_div(n_points, kColorBruteThreads)),
+                           dim3(kColorBruteThreads), 0, s, a, verts, n_verts, faces, n_faces);
+      });
 }
 
 }  // extern "C"

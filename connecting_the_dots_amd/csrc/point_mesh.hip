@@ -60,6 +60,7 @@
 #include "../../include/ctd_hip_mesh_dist.h"
 #include "ctd_bvh.h"
 #include "ctd_common.h"
+#include "ctd_mesh_query.h"
 #include "ctd_point_tri.h"
 
 namespace ctd {
@@ -102,22 +103,7 @@ __global__ __launch_bounds__(kBruteThreads) void point_mesh_brute_kernel(const f
   Nearest best = nearest_none();
   for (int base = 0; base < n_faces; base += kBruteThreads) {
     __syncthreads();                                   // the previous tile has been read by every lane
-    const int j = base + tid;
-    int valid = 0;
-    if (j < n_faces) {
-      const int i0 = faces[(long)j * 3], i1 = faces[(long)j * 3 + 1], i2 = faces[(long)j * 3 + 2];
-      valid = i0 >= 0 && i0 < n_verts && i1 >= 0 && i1 < n_verts && i2 >= 0 && i2 < n_verts;
-      if (valid) {
-        const float *a = verts + (long)i0 * 3, *b = verts + (long)i1 * 3, *c = verts + (long)i2 * 3;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          tri[tid * 9 + k] = a[k];
-          tri[tid * 9 + 3 + k] = b[k];
-          tri[tid * 9 + 6 + k] = c[k];
-        }
-      }
-    }
-    ok[tid] = valid;
+    face_tile_load<kBruteThreads>(tri, ok, base, verts, n_verts, faces, n_faces);
     __syncthreads();
     if (!live) continue;
     const int cnt = min(kBruteThreads, n_faces - base);
@@ -157,8 +143,7 @@ __device__ inline float node_bound2(const float* p, float4 b0, float4 b1) {
 __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const float* __restrict__ points, int n_points,
                                                             float* __restrict__ d2, int* __restrict__ face,
                                                             float* __restrict__ closest) {
-  __shared__ int stack_lds[kStack * 64];
-  int* stack = stack_lds + threadIdx.x;
+  int* stack = lane_stack();
   const long i = (long)blockIdx.x * 64 + threadIdx.x;
   if (i >= n_points) return;
   const float p[3] = {points[i * 3], points[i * 3 + 1], points[i * 3 + 2]};
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const fl
   while (true) {
     if (cur < 0) {                                     // pop until a node survives the best as it is now
       while (sp > 0) {
-        const int cand = stack[(--sp) * 64];
+        const int cand = lane_at(stack, --sp);
         if (exact && node_bound2(p, bv.box[(long)cand * 2], bv.box[(long)cand * 2 + 1]) > best.d2) continue;
         cur = cand;
         break;
@@ -179,10 +164,8 @@ __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const fl
     if (m.x < 0) {
       const int first = -(m.x + 1);
       for (int k = 0; k < m.y; ++k) {
-        const float4 a = bv.tris[(long)(first + k) * 3], b = bv.tris[(long)(first + k) * 3 + 1],
-                     c = bv.tris[(long)(first + k) * 3 + 2];
-        const float v0[3] = {a.x, a.y, a.z}, v1[3] = {b.x, b.y, b.z}, v2[3] = {c.x, c.y, c.z};
-        const int f = __float_as_int(a.w);
+        float v0[3], v1[3], v2[3];
+        const int f = bvh_leaf_tri(bv, first + k, v0, v1, v2);
         const PointTri r = point_tri(p, v0, v1, v2);
         if (r.d2 < best.d2 || (r.d2 == best.d2 && f < best.face)) {
           best.d2 = r.d2;
@@ -201,30 +184,13 @@ __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const fl
     const bool keep_l = !(bl > best.d2), keep_r = !(br > best.d2);
     if (keep_l && keep_r) {
       const bool right_first = br < bl;
-      if (sp < kStack) stack[(sp++) * 64] = right_first ? m.x : m.y;   // always true for depth <= kMaxDepth
+      if (sp < kStack) lane_at(stack, sp++) = right_first ? m.x : m.y;        // always true for depth <= kMaxDepth
       cur = right_first ? m.y : m.x;
     } else {
       cur = keep_l ? m.x : (keep_r ? m.y : -1);
     }
   }
   nearest_store(best, i, d2, face, closest);
-}
-
-static int point_mesh_distance_f32(const float* points, int n_points, const float* verts, int n_verts, const int* faces,
-                                   int n_faces, const void* bvh, float* d2, int* face, float* closest,
-                                   hipStream_t stream) {
-  if (bvh && n_faces > 0) {
-    const int st = bvh_check(bvh, n_faces, stream);
-    if (st != CTD_OK) return st;
-    hipLaunchKernelGGL(point_mesh_bvh_kernel, dim3((unsigned)ceil_div(n_points, 64)), dim3(64), 0, stream,
-                       bvh_view(bvh, n_faces), points, n_points, d2, face, closest);
-    CTD_LAUNCH_CHECK();
-    return CTD_OK;
-  }
-  hipLaunchKernelGGL(point_mesh_brute_kernel, dim3((unsigned)ceil_div(n_points, kBruteThreads)), dim3(kBruteThreads), 0,
-                     stream, points, n_points, verts, n_verts, faces, n_faces, d2, face, closest);
-  CTD_LAUNCH_CHECK();
-  return CTD_OK;
 }
 
 }  // namespace ctd
@@ -239,13 +205,21 @@ int ctd_point_mesh_distance_f32(const float* points, int n_points, const float* 
   if (n_points < 0 || n_verts < 0 || n_faces < 0) return CTD_ERR_INVALID_ARG;
   if ((double)n_points * 3 >= 2147483648.0 || n_faces > kBvhMaxFaces) return CTD_ERR_INVALID_ARG;
   if (n_points > 0 && (!points || !d2 || !face)) return CTD_ERR_INVALID_ARG;
-  if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return CTD_ERR_INVALID_ARG;
-  if (bvh && (uintptr_t)bvh % 16) return CTD_ERR_INVALID_ARG;
+  if (!mesh_group_ok(verts, n_verts, faces, n_faces, bvh)) return CTD_ERR_INVALID_ARG;
   if (n_points == 0) return CTD_OK;
   DeviceGuard g(device);
   if (g.status) return g.status;
-  return point_mesh_distance_f32(points, n_points, verts, n_verts, faces, n_faces, bvh, d2, face, closest,
-                                 (hipStream_t)stream);
+  const hipStream_t s = (hipStream_t)stream;
+  return tree_or_brute(
+      bvh, n_faces, s,
+      [&](const BvhView& bv) {
+        hipLaunchKernelGGL(point_mesh_bvh_kernel, dim3((unsigned)ceil_div(n_points, 64)), dim3(64), 0, s, bv, points,
+                           n_points, d2, face, closest);
+      },
+      [&] {
+        hipLaunchKernelGGL(point_mesh_brute_kernel, dim3((unsigned)ceil_div(n_points, kBruteThreads)),
+                           dim3(kBruteThreads), 0, s, points, n_points, verts, n_verts, faces, n_faces, d2, face, closest);
+      });
 }
 
 }  // extern "C"

@@ -33,11 +33,12 @@
 #include "ctd_bvh.h"
 #include "ctd_bvh_ray.h"
 #include "ctd_common.h"
+#include "ctd_mesh_query.h"
 #include "ctd_render.h"
 
 namespace ctd {
 
-// the buffer's layout, its view, the header check and the stack depth they share with point_mesh.hip: ctd_bvh.h
+// the buffer's layout, view, header check and stack depth: ctd_bvh.h; the leaf fetch and the lane stack: ctd_mesh_query.h
 constexpr int kLeafFaces = 4;       // a node over <= kLeafFaces sorted faces is a leaf
 constexpr int kSortThreads = 256, kSortItems = 16, kSortTile = kSortThreads * kSortItems;
 constexpr int kDigitBits = 4, kDigits = 1 << kDigitBits, kKeyBits = 63;
@@ -364,20 +365,17 @@ __device__ inline Hit bvh_nearest(const BvhView& bv, int* __restrict__ stack, co
   if (bv.n == 0) return h;
   const bool exact = finite3(o) && finite3(d);       // non-finite rays visit every face (nothing prunes them)
   const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) * 1.00001f;
-  int sp = 0;
-  stack[0] = 0;
-  sp = 1;
+  int sp = 1;
+  lane_at(stack, 0) = 0;
   while (sp > 0) {
-    const int node = stack[(--sp) * 64];
+    const int node = lane_at(stack, --sp);
     if (exact && prune(o, d, dn, bv.box[(long)node * 2], bv.box[(long)node * 2 + 1], h.valid ? h.t : FLT_MAX)) continue;
     const int4 m = bv.meta[node];
     if (m.x < 0) {
       const int first = -(m.x + 1);
       for (int k = 0; k < m.y; ++k) {
-        const float4 a = bv.tris[(long)(first + k) * 3], b = bv.tris[(long)(first + k) * 3 + 1],
-                     c = bv.tris[(long)(first + k) * 3 + 2];
-        const float v0[3] = {a.x, a.y, a.z}, v1[3] = {b.x, b.y, b.z}, v2[3] = {c.x, c.y, c.z};
-        const int f = __float_as_int(a.w);
+        float v0[3], v1[3], v2[3];
+        const int f = bvh_leaf_tri(bv, first + k, v0, v1, v2);
         float ft, fu, fv;
         if (ray_tri(o, d, v0, v1, v2, ft, fu, fv) && (ft < h.t || (ft == h.t && h.valid && f < h.face))) {
           h.t = ft;
@@ -388,8 +386,8 @@ __device__ inline Hit bvh_nearest(const BvhView& bv, int* __restrict__ stack, co
         }
       }
     } else if (sp + 2 <= kStack) {                    // always true for depth <= kMaxDepth (checked at launch)
-      stack[(sp++) * 64] = m.y;
-      stack[(sp++) * 64] = m.x;
+      lane_at(stack, sp++) = m.y;
+      lane_at(stack, sp++) = m.x;
     }
   }
   return h;
@@ -408,8 +406,7 @@ __global__ __launch_bounds__(64) void render_proj_bvh_kernel(BvhView bv, const f
                                                              float alpha, const float* __restrict__ pattern,
                                                              float d_alpha, float d_beta, float* __restrict__ depth,
                                                              float* __restrict__ color, float* __restrict__ normal) {
-  __shared__ int stack_lds[kStack * 64];
-  int* stack = stack_lds + threadIdx.x;
+  int* stack = lane_stack();
   int h, w;
   if (!tile_pixel(cam.width, cam.height, h, w)) return;
   const int idx = h * cam.width + w;
@@ -437,8 +434,7 @@ __global__ __launch_bounds__(64) void render_mesh_bvh_kernel(BvhView bv, const f
                                                              const int* __restrict__ faces, CamDev cam, float ka,
                                                              float kd, float ks, float alpha, float* __restrict__ depth,
                                                              float* __restrict__ color, float* __restrict__ normal) {
-  __shared__ int stack_lds[kStack * 64];
-  int* stack = stack_lds + threadIdx.x;
+  int* stack = lane_stack();
   int h, w;
   if (!tile_pixel(cam.width, cam.height, h, w)) return;
   const int idx = h * cam.width + w;

@@ -38,12 +38,23 @@ class TsdfMesh:
         self.n_verts_per_track, self.n_faces_per_track = n_verts_per_track, n_faces_per_track
         self._counts = counts                                   # host copy: [(n_verts, n_faces)] per track
 
+    @property
+    def n_tracks(self):
+        return len(self._counts)
+
+    def tracks(self):
+        """-> (b, verts_b, faces_b, normals_b, v0) for every track in order: the slices of `track(b)`, and the row of
+        verts, src and normals at which the track's vertices start.  No copy and no synchronisation."""
+        v0 = 0
+        for b, (nv, _) in enumerate(self._counts):
+            yield (b,) + self.track(b) + (v0,)
+            v0 += nv
+
     def track(self, b):
         """-> (verts_b [n,3] f32, faces_b [k,3] int32, normals_b [n,3] f32 or None): contiguous slices, no copy and no
         synchronisation; they go straight into `renderer.MeshBVH(verts_b, faces_b)` and `renderer.render_mesh`."""
-        b = _integer(b, "b", "TsdfMesh.track", 0, len(self._counts) - 1, "an integer in [0, %d)" % len(self._counts))
-        v0 = sum(c[0] for c in self._counts[:b])
-        f0 = sum(c[1] for c in self._counts[:b])
+        b = _integer(b, "b", "TsdfMesh.track", 0, self.n_tracks - 1, "an integer in [0, %d)" % self.n_tracks)
+        v0, f0 = (sum(c[k] for c in self._counts[:b]) for k in (0, 1))
         nv, nf = self._counts[b]
         return (self.verts[v0:v0 + nv], self.faces[f0:f0 + nf],
                 None if self.normals is None else self.normals[v0:v0 + nv])

@@ -15,9 +15,7 @@ them cheaper.  No fallback to torch: a missing kernel is an error.
 import torch
 
 from . import _lib
-from .mesh import TsdfMesh
-from .mesheval import _nx3
-from .renderer import CTD_ERR_UNSUPPORTED, MeshBVH
+from ._meshargs import _call_tree_then_brute, _cat_or_empty, _flag, _nx3, _resolve_bvh, _tsdf_mesh_arg
 from .torchext._common import _check, _number, _ptr, _same_device, _stream
 
 IN_IMAGE, FACING, UNOCCLUDED, USED = 1, 2, 4, 7
@@ -49,23 +47,6 @@ class ViewColors:
 
     def __init__(self, color, weight, n_views, flags):
         self.color, self.weight, self.n_views, self.flags = color, weight, n_views, flags
-
-
-def _resolve_bvh(bvh, verts, faces, who):
-    """-> a usable MeshBVH of these tensors, or None (brute force); as mesheval._resolve_bvh, with this module's threshold"""
-    if bvh is None:
-        return None
-    if isinstance(bvh, str):
-        if bvh != "auto":
-            raise RuntimeError("%s: bvh must be None, 'auto' or a renderer.MeshBVH" % who)
-        if faces.shape[0] < AUTO_BVH_MIN_FACES or bool(((faces < 0) | (faces >= verts.shape[0])).any()):
-            return None                                   # small, or faces the tree's build may not read
-        bvh = MeshBVH(verts, faces)
-    elif not isinstance(bvh, MeshBVH):
-        raise RuntimeError("%s: bvh must be None, 'auto' or a renderer.MeshBVH" % who)
-    elif not bvh.matches(verts, faces):
-        raise RuntimeError("%s: bvh was built from other verts / faces tensors" % who)
-    return bvh if bvh.usable else None
 
 
 def _views(images, K, R, t, who, lead=()):
@@ -102,8 +83,7 @@ def _scalars(margin, min_cos, mode, return_flags, who):
         raise RuntimeError("%s: min_cos must lie in [0, 1)" % who)
     if mode not in _MODES:
         raise RuntimeError("%s: unknown mode %r (mean | best)" % (who, mode))
-    if not isinstance(return_flags, bool):
-        raise RuntimeError("%s: return_flags must be True or False" % who)
+    _flag(return_flags, "return_flags", who)
     return margin, min_cos, _MODES[mode]
 
 
@@ -147,23 +127,17 @@ def view_colors(points, images, K, R, t, margin, verts=None, faces=None, normals
     _same_device(points, *others)
     if 3 * n >= 2 ** 31 or n * V >= 2 ** 31 or V * C * H * W >= 2 ** 31:
         raise RuntimeError("%s: 3 * the number of points, points * views and V * C * H * W must stay below 2^31" % who)
-    tree = _resolve_bvh(bvh, verts, faces, who)
+    tree = _resolve_bvh(bvh, verts, faces, who, AUTO_BVH_MIN_FACES)
     color = torch.empty((n, C), dtype=torch.float32, device=dev)
     weight = torch.empty((n,), dtype=torch.float32, device=dev)
     n_views = torch.empty((n,), dtype=torch.int32, device=dev)
     flags = torch.empty((n, V), dtype=torch.uint8, device=dev) if return_flags else None
     if n == 0:
         return ViewColors(color, weight, n_views, flags)
-    fn = _lib.lib().ctd_mesh_view_colors_f32
     args = (_ptr(points), _ptr(normals), n, _ptr(images), _ptr(valid), _ptr(K), _ptr(R), _ptr(t), V, C, H, W,
             _ptr(verts) or None, verts.shape[0], _ptr(faces) or None, faces.shape[0])
     rest = (margin, min_cos, mode, _ptr(color), _ptr(weight), _ptr(n_views), _ptr(flags), dev.index, _stream(dev))
-    st = CTD_ERR_UNSUPPORTED
-    if tree is not None:
-        st = fn(*args, _ptr(tree.buffer), *rest)
-    if st == CTD_ERR_UNSUPPORTED:                         # no tree, or one deeper than the traversal stack
-        st = fn(*args, None, *rest)
-    _lib.check(st, who)
+    _call_tree_then_brute(_lib.lib().ctd_mesh_view_colors_f32, args, tree, rest, who)
     return ViewColors(color, weight, n_views, flags)
 
 
@@ -176,25 +150,22 @@ def color_tsdf_mesh(m, images, K, R, t, margin, valid=None, min_cos=0.0, mode="m
     track on m.track(b): `view_colors` of the track's vertices against the track's own mesh (bvh='auto'), with m.normals
     when the mesh has them.  margin as for `view_colors`: for a TSDF mesh a voxel or two."""
     who = "color_tsdf_mesh"
-    if not isinstance(m, TsdfMesh):
-        raise RuntimeError("%s: m must be a mesh.TsdfMesh" % who)
-    B = len(m._counts)
+    B = _tsdf_mesh_arg(m, who).n_tracks
     images, V, C, H, W = _views(images, K, R, t, who, lead=(B,))
     _scalars(margin, min_cos, mode, return_flags, who)
     if valid is not None:
         _check(valid, "%s: valid" % who, (torch.uint8,))
         if tuple(valid.shape) != (B, V, H, W):
             raise RuntimeError("%s: valid must be shaped [B,V,H,W] = %s, got %s" % (who, (B, V, H, W), tuple(valid.shape)))
-    dev = _same_device(m.verts, images, K, R, t, *(() if valid is None else (valid,)))
+    _same_device(m.verts, images, K, R, t, *(() if valid is None else (valid,)))
     parts = []
-    for b in range(B):
-        verts, faces, normals = m.track(b)
+    for b, verts, faces, normals, _ in m.tracks():
         parts.append(view_colors(verts, images[b], K, R[b], t[b], margin, verts, faces, normals=normals,
                                  valid=None if valid is None else valid[b], min_cos=min_cos, mode=mode, bvh="auto",
                                  return_flags=return_flags))
 
     def cat(name, shape, dtype):
-        return torch.cat([getattr(p, name) for p in parts]) if parts else torch.empty(shape, dtype=dtype, device=dev)
+        return _cat_or_empty([getattr(p, name) for p in parts], m.verts.new_empty(shape, dtype=dtype))
 
     return ViewColors(cat("color", (0, C), torch.float32), cat("weight", (0,), torch.float32),
                       cat("n_views", (0,), torch.int32), cat("flags", (0, V), torch.uint8) if return_flags else None)

@@ -12,8 +12,8 @@ them cheaper.  No fallback to torch: a missing kernel is an error.
 import torch
 
 from . import _lib
-from .renderer import CTD_ERR_UNSUPPORTED, MeshBVH
-from .torchext._common import _check, _integer, _number, _ptr, _same_device, _stream
+from ._meshargs import _call_tree_then_brute, _flag, _nx3, _resolve_bvh
+from .torchext._common import _integer, _number, _ptr, _same_device, _stream
 
 # 'auto' builds a tree from this many faces on.  profiles/point_mesh.txt (10^5 near-surface points, brute force against
 # build + traversal): the tree loses at 1 172 faces (0.58) and wins at 3 850 (1.24), the crossover is near 2 800; rounded
@@ -30,52 +30,6 @@ _RULE = """
     bits on every run, with a tree or without."""
 
 
-def _nx3(t, who, name, dtype):
-    _check(t, "%s: %s" % (who, name), (dtype,))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise RuntimeError("%s: %s must be shaped [n,3], got %s" % (who, name, tuple(t.shape)))
-    return t
-
-
-def _resolve_bvh(bvh, verts, faces, who):
-    """-> a usable MeshBVH of these tensors, or None (brute force)"""
-    if bvh is None:
-        return None
-    if isinstance(bvh, str):
-        if bvh != "auto":
-            raise RuntimeError("%s: bvh must be None, 'auto' or a renderer.MeshBVH" % who)
-        if faces.shape[0] < AUTO_BVH_MIN_FACES or bool(((faces < 0) | (faces >= verts.shape[0])).any()):
-            return None                                   # small, or faces the tree's build may not read
-        bvh = MeshBVH(verts, faces)
-    elif not isinstance(bvh, MeshBVH):
-        raise RuntimeError("%s: bvh must be None, 'auto' or a renderer.MeshBVH" % who)
-    elif not bvh.matches(verts, faces):
-        raise RuntimeError("%s: bvh was built from other verts / faces tensors" % who)
-    return bvh if bvh.usable else None
-
-
-def _query(points, verts, faces, bvh, return_closest, who):
-    dev = points.device
-    n = points.shape[0]
-    if 3 * n >= 2 ** 31:
-        raise RuntimeError("%s: 3 * the number of points must stay below 2^31" % who)
-    d2 = torch.empty((n,), dtype=torch.float32, device=dev)
-    face = torch.empty((n,), dtype=torch.int32, device=dev)
-    closest = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_closest else None
-    if n == 0:
-        return d2, face, closest
-    fn = _lib.lib().ctd_point_mesh_distance_f32
-    args = (_ptr(points), n, _ptr(verts) or None, verts.shape[0], _ptr(faces) or None, faces.shape[0])
-    out = (_ptr(d2), _ptr(face), _ptr(closest), dev.index, _stream(dev))
-    st = CTD_ERR_UNSUPPORTED
-    if bvh is not None:
-        st = fn(*args, _ptr(bvh.buffer), *out)
-    if st == CTD_ERR_UNSUPPORTED:                         # no tree, or one deeper than the traversal stack
-        st = fn(*args, None, *out)
-    _lib.check(st, who)
-    return d2, face, closest
-
-
 def point_mesh_distance(points, verts, faces, bvh=None, return_closest=False):
     """For every row of points f32 [n,3] the nearest face of the mesh verts f32 [m,3], faces int32 [k,3] (CUDA tensors) ->
     (dist f32 [n], face int32 [n]) and, with return_closest, closest f32 [n,3].  bvh: None (brute force over all faces),
@@ -86,10 +40,19 @@ def point_mesh_distance(points, verts, faces, bvh=None, return_closest=False):
     _nx3(points, who, "points", torch.float32)
     _nx3(verts, who, "verts", torch.float32)
     _nx3(faces, who, "faces", torch.int32)
-    _same_device(points, verts, faces)
-    if not isinstance(return_closest, bool):
-        raise RuntimeError("%s: return_closest must be True or False" % who)
-    d2, face, closest = _query(points, verts, faces, _resolve_bvh(bvh, verts, faces, who), return_closest, who)
+    dev = _same_device(points, verts, faces)
+    _flag(return_closest, "return_closest", who)
+    tree = _resolve_bvh(bvh, verts, faces, who, AUTO_BVH_MIN_FACES)
+    n = points.shape[0]
+    if 3 * n >= 2 ** 31:
+        raise RuntimeError("%s: 3 * the number of points must stay below 2^31" % who)
+    d2 = torch.empty((n,), dtype=torch.float32, device=dev)
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    closest = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_closest else None
+    if n > 0:
+        args = (_ptr(points), n, _ptr(verts) or None, verts.shape[0], _ptr(faces) or None, faces.shape[0])
+        out = (_ptr(d2), _ptr(face), _ptr(closest), dev.index, _stream(dev))
+        _call_tree_then_brute(_lib.lib().ctd_point_mesh_distance_f32, args, tree, out, who)
     dist = torch.sqrt(d2)
     return (dist, face, closest) if return_closest else (dist, face)
 

@@ -12,8 +12,9 @@ All of it is integer work: the outputs are exact and the same on every run.  No 
 import torch
 
 from . import _lib
+from ._meshargs import _cat_or_empty, _flag, _nx3, _ptr_or, _tsdf_mesh_arg
 from .mesh import TsdfMesh
-from .torchext._common import _call, _check, _integer, _ptr, _same_device, _stream, _workspace
+from .torchext._common import _call, _integer, _ptr, _same_device, _stream, _workspace
 
 _RULE = """
     The rule (include/ctd_hip_mesh_clean.h).  A face is valid when its three indices lie in [0, n_verts), are pairwise
@@ -28,33 +29,6 @@ _RULE = """
     in an otherwise closed mesh.  The same bits on every run."""
 
 
-def _faces_arg(faces, who):
-    _check(faces, "%s: faces" % who, (torch.int32,))
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise RuntimeError("%s: faces must be shaped [m,3], got %s" % (who, tuple(faces.shape)))
-    return faces
-
-
-def _verts_arg(verts, who, name="verts", rows=None):
-    _check(verts, "%s: %s" % (who, name), (torch.float32,))
-    if verts.dim() != 2 or verts.shape[1] != 3 or (rows is not None and verts.shape[0] != rows):
-        raise RuntimeError("%s: %s must be shaped [%s,3], got %s" % (who, name, "n" if rows is None else rows,
-                                                                     tuple(verts.shape)))
-    return verts
-
-
-def _flag(x, name, who):
-    if not isinstance(x, bool):
-        raise RuntimeError("%s: %s must be True or False" % (who, name))
-    return int(x)
-
-
-def _ptr_or(t, spare):
-    """an empty tensor has no storage, but the C calls want their required pointers all the same (they read and write
-    nothing through them then): the workspace stands in"""
-    return t.data_ptr() or spare.data_ptr()
-
-
 def _sizes_ok(n_verts, n_faces, who):
     if 3 * n_faces >= 2 ** 31:
         raise RuntimeError("%s: 3 * the number of faces must stay below 2^31" % who)
@@ -66,13 +40,13 @@ def mesh_components(faces, n_verts, verts=None, drop_degenerate=False):
     n_components int).  verts f32 [n_verts,3] is needed with drop_degenerate only.  One call, one synchronisation (to
     read n_components)."""
     who = "mesh_components"
-    faces = _faces_arg(faces, who)
+    faces = _nx3(faces, who, "faces", torch.int32, letter="m")
     n_verts = _integer(n_verts, "n_verts", who)
     drop = _flag(drop_degenerate, "drop_degenerate", who)
     if drop and verts is None:
         raise RuntimeError("%s: drop_degenerate needs verts" % who)
     if verts is not None:
-        _verts_arg(verts, who, rows=n_verts)
+        _nx3(verts, who, "verts", torch.float32, n_verts)
         _same_device(faces, verts)
     dev, m = faces.device, faces.shape[0]
     L = _lib.lib()
@@ -105,10 +79,10 @@ def mesh_clean(verts, faces, min_faces=1, keep_largest=False, drop_degenerate=Tr
     `CleanMesh`.  One call, one synchronisation to read the counts; the returned tensors own exactly their size.  Not
     differentiable."""
     who = "mesh_clean"
-    verts, faces = _verts_arg(verts, who), _faces_arg(faces, who)
+    verts, faces = _nx3(verts, who, "verts", torch.float32), _nx3(faces, who, "faces", torch.int32, letter="m")
     n, m = verts.shape[0], faces.shape[0]
     if normals is not None:
-        _verts_arg(normals, who, "normals", rows=n)
+        _nx3(normals, who, "normals", torch.float32, n)
     dev = _same_device(verts, faces, *(() if normals is None else (normals,)))
     min_faces = _integer(min_faces, "min_faces", who, 1)
     largest, drop = _flag(keep_largest, "keep_largest", who), _flag(drop_degenerate, "drop_degenerate", who)
@@ -136,23 +110,20 @@ def clean_tsdf_mesh(m, min_faces=1, keep_largest=False, drop_degenerate=True):
     vertices, faces remapped and track-local, the counts rebuilt, so that `.track(b)`, `renderer.MeshBVH` and
     `mesh.save_ply` work on the result.  Track by track: one call and one synchronisation per track."""
     who = "clean_tsdf_mesh"
-    if not isinstance(m, TsdfMesh):
-        raise RuntimeError("%s: m must be a mesh.TsdfMesh" % who)
+    _tsdf_mesh_arg(m, who)
     min_faces = _integer(min_faces, "min_faces", who, 1)
     _flag(keep_largest, "keep_largest", who)
     _flag(drop_degenerate, "drop_degenerate", who)
     dev = m.verts.device
-    parts, counts, v0 = [], [], 0
-    for b in range(len(m._counts)):
-        verts, faces, normals = m.track(b)
+    parts, counts = [], []
+    for _, verts, faces, normals, v0 in m.tracks():
         c = mesh_clean(verts, faces, min_faces, keep_largest, drop_degenerate, normals)
         src = m.src[v0:v0 + verts.shape[0]].index_select(0, c.vert_index.long())
         parts.append((c.verts, src, c.normals, c.faces))
         counts.append((c.verts.shape[0], c.faces.shape[0]))
-        v0 += verts.shape[0]
 
     def cat(k, like):
-        return torch.cat([p[k] for p in parts]) if parts else like[:0].clone()
+        return _cat_or_empty([p[k] for p in parts], like)
 
     n_verts = torch.tensor([c[0] for c in counts], dtype=torch.int64, device=dev)
     n_faces = torch.tensor([c[1] for c in counts], dtype=torch.int64, device=dev)

@@ -14,8 +14,8 @@ a missing kernel is an error.  Nothing is differentiable.
 import torch
 
 from . import _lib
+from ._meshargs import _cat_or_empty, _flag, _nx3, _ptr_or, _tsdf_mesh_arg
 from .mesh import TsdfMesh
-from .meshops import _faces_arg, _flag, _ptr_or, _verts_arg
 from .torchext._common import _call, _integer, _number, _ptr, _same_device, _stream, _workspace
 
 REFERENCED, BOUNDARY, NONMANIFOLD = 1, 2, 4                     # the bits of MeshAdjacency.vflags
@@ -51,7 +51,7 @@ class MeshAdjacency:
 
     def __init__(self, faces, n_verts):
         who = "MeshAdjacency"
-        faces = _faces_arg(faces, who)
+        faces = _nx3(faces, who, "faces", torch.int32, letter="m")
         n = _integer(n_verts, "n_verts", who)
         dev, m = faces.device, faces.shape[0]
         L = _lib.lib()
@@ -110,7 +110,7 @@ def mesh_smooth(verts, faces, iters=10, lam=0.5, mu=-0.53, fix_boundary=True, ad
     fix_boundary the vertices at the ends of boundary edges stay where they are.  adjacency: a `MeshAdjacency` of these
     faces (built here when None: one synchronisation; none otherwise).  Not differentiable."""
     who = "mesh_smooth"
-    verts, faces = _verts_arg(verts, who), _faces_arg(faces, who)
+    verts, faces = _nx3(verts, who, "verts", torch.float32), _nx3(faces, who, "faces", torch.int32, letter="m")
     dev = _same_device(verts, faces)
     iters, lam, mu, fix = _smooth_args(iters, lam, mu, fix_boundary, who)
     n = verts.shape[0]
@@ -131,7 +131,7 @@ def vertex_normals(verts, faces, adjacency=None):
     face uses or whose faces have no area.  adjacency: a `MeshAdjacency` of these faces (built here when None: one
     synchronisation; none otherwise).  Not differentiable."""
     who = "vertex_normals"
-    verts, faces = _verts_arg(verts, who), _faces_arg(faces, who)
+    verts, faces = _nx3(verts, who, "verts", torch.float32), _nx3(faces, who, "faces", torch.int32, letter="m")
     dev = _same_device(verts, faces)
     n = verts.shape[0]
     adj = _adjacency(adjacency, faces, n, who)
@@ -151,19 +151,16 @@ def smooth_tsdf_mesh(m, iters=10, lam=0.5, mu=-0.53, fix_boundary=True, recomput
     unchanged; normals are the `vertex_normals` of the smoothed mesh when m.normals is not None and recompute_normals is
     set (else m.normals as they are).  Track by track: one adjacency, so one synchronisation, per track."""
     who = "smooth_tsdf_mesh"
-    if not isinstance(m, TsdfMesh):
-        raise RuntimeError("%s: m must be a mesh.TsdfMesh" % who)
+    _tsdf_mesh_arg(m, who)
     _smooth_args(iters, lam, mu, fix_boundary, who)
     renew = _flag(recompute_normals, "recompute_normals", who) and m.normals is not None
-    verts_out, normals_out = [], []
-    for b in range(len(m._counts)):
-        verts, faces, _ = m.track(b)
+    verts_out, normals_out, counts = [], [], []
+    for _, verts, faces, _, _ in m.tracks():
+        counts.append((verts.shape[0], faces.shape[0]))
         adj = MeshAdjacency(faces, verts.shape[0])
         verts_out.append(mesh_smooth(verts, faces, iters, lam, mu, fix_boundary, adjacency=adj))
         if renew:
             normals_out.append(vertex_normals(verts_out[-1], faces, adjacency=adj))
-    verts = torch.cat(verts_out) if verts_out else m.verts.clone()
-    normals = m.normals
-    if renew:
-        normals = torch.cat(normals_out) if normals_out else m.normals.clone()
-    return TsdfMesh(verts, m.src, normals, m.faces, m.n_verts_per_track, m.n_faces_per_track, list(m._counts))
+    normals = _cat_or_empty(normals_out, m.normals) if renew else m.normals
+    return TsdfMesh(_cat_or_empty(verts_out, m.verts), m.src, normals, m.faces, m.n_verts_per_track, m.n_faces_per_track,
+                    counts)

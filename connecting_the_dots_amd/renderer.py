@@ -20,8 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-CTD_ERR_UNSUPPORTED = 3
+from ._meshargs import CTD_ERR_UNSUPPORTED, _cuda_tensors
 
 
 def _cam_params(fx, fy, px, py, R, t):
@@ -128,62 +127,51 @@ def _check_bvh(bvh, verts, faces):
     return bvh.usable
 
 
+def _render(brute, tree, who, bvh, verts, faces, args):
+    """brute(*args), or with a usable tree of these tensors tree(the tree's buffer, *args)"""
+    if bvh is not None and _check_bvh(bvh, verts, faces):
+        _lib.check(tree(bvh.buffer.data_ptr(), *args), who + " (bvh)")
+    else:
+        _lib.check(brute(*args), who)
+
+
 def render_mesh_proj(verts, colors, faces, cam, proj, shader, pattern, d_alpha=1.0, d_beta=0.0, bvh=None):
     """verts, colors [n,3] f32, faces [m,3] int32, pattern [ph,pw,3] f32: CUDA tensors; cam, proj: PyCamera; shader:
     PyShader -> (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors (normal zero where nothing is hit).
     bvh: a MeshBVH of these verts / faces, or None (brute force); both give the same bits."""
-    for t_, name, dt in ((verts, "verts", torch.float32), (colors, "colors", torch.float32), (faces, "faces", torch.int32),
-                         (pattern, "pattern", torch.float32)):
-        if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.is_contiguous() and t_.dtype == dt):
-            raise RuntimeError("%s must be a contiguous CUDA tensor of dtype %s" % (name, dt))
+    _cuda_tensors((verts, "verts", torch.float32), (colors, "colors", torch.float32), (faces, "faces", torch.int32),
+                  (pattern, "pattern", torch.float32))
     if tuple(pattern.shape) != (proj.height, proj.width, 3):
         raise Exception('pattern has to be a %dx%dx3 tensor' % (proj.height, proj.width))      # cyrender.pyx:197
     dev = verts.device
     depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
     color = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
     normal = torch.zeros((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
-    if bvh is not None and _check_bvh(bvh, verts, faces):
-        st = _lib.lib().ctd_render_mesh_proj_bvh_f32(
-            bvh.buffer.data_ptr(), verts.data_ptr(), colors.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
+    args = (verts.data_ptr(), colors.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
             cam.params.ctypes.data, cam.width, cam.height, proj.params.ctypes.data, proj.width, proj.height,
-            shader.params.ctypes.data, pattern.data_ptr(), float(d_alpha), float(d_beta), depth.data_ptr(),
-            color.data_ptr(), normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "render_mesh_proj (bvh)")
-        return depth, color, normal
-    st = _lib.lib().ctd_render_mesh_proj_f32(
-        verts.data_ptr(), colors.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
-        cam.params.ctypes.data, cam.width, cam.height, proj.params.ctypes.data, proj.width, proj.height,
-        shader.params.ctypes.data, pattern.data_ptr(), float(d_alpha), float(d_beta), depth.data_ptr(), color.data_ptr(),
-        normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "render_mesh_proj")
+            shader.params.ctypes.data, pattern.data_ptr(), float(d_alpha), float(d_beta), depth.data_ptr(), color.data_ptr(),
+            normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    L = _lib.lib()
+    _render(L.ctd_render_mesh_proj_f32, L.ctd_render_mesh_proj_bvh_f32, "render_mesh_proj", bvh, verts, faces, args)
     return depth, color, normal
 
 
 def render_mesh(verts, colors, normals, faces, cam, shader, bvh=None):
     """RenderMeshFunctor (render.h:150-223): verts, colors, normals [n,3] f32, faces [m,3] int32 CUDA tensors ->
     (depth [H,W], color [H,W,3], normal [H,W,3]) CUDA tensors.  bvh: as for render_mesh_proj."""
-    for t_, name, dt in ((verts, "verts", torch.float32), (colors, "colors", torch.float32),
-                         (normals, "normals", torch.float32), (faces, "faces", torch.int32)):
-        if not (isinstance(t_, torch.Tensor) and t_.is_cuda and t_.is_contiguous() and t_.dtype == dt):
-            raise RuntimeError("%s must be a contiguous CUDA tensor of dtype %s" % (name, dt))
+    _cuda_tensors((verts, "verts", torch.float32), (colors, "colors", torch.float32), (normals, "normals", torch.float32),
+                  (faces, "faces", torch.int32))
     if colors.shape != verts.shape or normals.shape != verts.shape:
         raise RuntimeError("colors and normals must have one row per vertex")
     dev = verts.device
     depth = torch.empty((cam.height, cam.width), dtype=torch.float32, device=dev)
     color = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
     normal = torch.empty((cam.height, cam.width, 3), dtype=torch.float32, device=dev)
-    if bvh is not None and _check_bvh(bvh, verts, faces):
-        st = _lib.lib().ctd_render_mesh_bvh_f32(
-            bvh.buffer.data_ptr(), verts.data_ptr(), colors.data_ptr(), normals.data_ptr(), verts.shape[0],
-            faces.data_ptr(), faces.shape[0], cam.params.ctypes.data, cam.width, cam.height, shader.params.ctypes.data,
-            depth.data_ptr(), color.data_ptr(), normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(st, "render_mesh (bvh)")
-        return depth, color, normal
-    st = _lib.lib().ctd_render_mesh_f32(
-        verts.data_ptr(), colors.data_ptr(), normals.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
-        cam.params.ctypes.data, cam.width, cam.height, shader.params.ctypes.data, depth.data_ptr(), color.data_ptr(),
-        normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "render_mesh")
+    args = (verts.data_ptr(), colors.data_ptr(), normals.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0],
+            cam.params.ctypes.data, cam.width, cam.height, shader.params.ctypes.data, depth.data_ptr(), color.data_ptr(),
+            normal.data_ptr(), dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    L = _lib.lib()
+    _render(L.ctd_render_mesh_f32, L.ctd_render_mesh_bvh_f32, "render_mesh", bvh, verts, faces, args)
     return depth, color, normal
 
 

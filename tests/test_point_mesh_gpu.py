@@ -293,7 +293,7 @@ def test_auto_none_and_an_explicit_tree_agree(monkeypatch):
     real = renderer.MeshBVH
     outs = [mesheval.point_mesh_distance(p, vt, ft, bvh=None, return_closest=True)]
     outs.append(mesheval.point_mesh_distance(p, vt, ft, bvh=real(vt, ft), return_closest=True))
-    monkeypatch.setattr(mesheval, "MeshBVH", lambda *a, **k: built.append(1) or real(*a, **k))     # counts 'auto' builds
+    monkeypatch.setattr(renderer, "MeshBVH", lambda *a, **k: built.append(1) or real(*a, **k))     # counts 'auto' builds
     outs.append(mesheval.point_mesh_distance(p, vt, ft, bvh="auto", return_closest=True))
     assert len(built) == (len(f) >= mesheval.AUTO_BVH_MIN_FACES)
     monkeypatch.setattr(mesheval, "AUTO_BVH_MIN_FACES", 1024)

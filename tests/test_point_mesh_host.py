@@ -117,7 +117,8 @@ def _fake_bvh(verts, faces, usable=True):
 
 
 def test_mesheval_rejections_need_no_gpu():
-    from connecting_the_dots_amd import mesheval
+    from connecting_the_dots_amd import _meshargs, mesheval
+    resolve = lambda *a: _meshargs._resolve_bvh(*a, mesheval.AUTO_BVH_MIN_FACES)      # noqa: E731  as point_mesh_distance calls it
     assert sorted(n for n in vars(mesheval) if not n.startswith("_") and
                   getattr(getattr(mesheval, n), "__module__", "") == mesheval.__name__) == [
         "point_mesh_distance", "reconstruction_error", "sample_surface"]
@@ -134,30 +135,30 @@ def test_mesheval_rejections_need_no_gpu():
     # a tree of other tensors, an unusable tree, a wrong kind of bvh
     other_v, other_f = v.clone(), f.clone()
     with pytest.raises(RuntimeError, match="other verts / faces"):
-        mesheval._resolve_bvh(_fake_bvh(other_v, f), v, f, "point_mesh_distance")
+        resolve(_fake_bvh(other_v, f), v, f, "point_mesh_distance")
     with pytest.raises(RuntimeError, match="other verts / faces"):
-        mesheval._resolve_bvh(_fake_bvh(v, other_f), v, f, "point_mesh_distance")
+        resolve(_fake_bvh(v, other_f), v, f, "point_mesh_distance")
     with pytest.raises(RuntimeError, match="other verts / faces"):
-        mesheval._resolve_bvh(_fake_bvh(v, f), v[:4], f, "point_mesh_distance")
+        resolve(_fake_bvh(v, f), v[:4], f, "point_mesh_distance")
     for bad in ("bvh", 3, (v, f)):
         with pytest.raises(RuntimeError, match="None, 'auto' or a renderer.MeshBVH"):
-            mesheval._resolve_bvh(bad, v, f, "point_mesh_distance")
+            resolve(bad, v, f, "point_mesh_distance")
     good = _fake_bvh(v, f)
-    assert mesheval._resolve_bvh(good, v, f, "x") is good and mesheval._resolve_bvh(None, v, f, "x") is None
-    assert mesheval._resolve_bvh(_fake_bvh(v, f, usable=False), v, f, "x") is None       # falls back to brute force
-    assert mesheval._resolve_bvh("auto", v, f, "x") is None                               # below the threshold: no build
+    assert resolve(good, v, f, "x") is good and resolve(None, v, f, "x") is None
+    assert resolve(_fake_bvh(v, f, usable=False), v, f, "x") is None       # falls back to brute force
+    assert resolve("auto", v, f, "x") is None                               # below the threshold: no build
     t = mesheval.AUTO_BVH_MIN_FACES
     assert t >= 2 and t & (t - 1) == 0                                                   # a power of two
 
 
 def test_shape_rejections_on_the_argument_helper():
     import unittest.mock as mock
-    from connecting_the_dots_amd import mesheval
-    with mock.patch.object(mesheval, "_check", lambda *a, **k: None):     # the device check comes first: step over it
+    from connecting_the_dots_amd import _meshargs
+    with mock.patch.object(_meshargs, "_check", lambda *a, **k: None):    # the device check comes first: step over it
         for bad in (torch.zeros(4), torch.zeros(4, 2), torch.zeros(2, 4, 3)):
             with pytest.raises(RuntimeError, match=r"must be shaped \[n,3\]"):
-                mesheval._nx3(bad, "point_mesh_distance", "points", torch.float32)
-        assert mesheval._nx3(torch.zeros(0, 3), "w", "points", torch.float32).shape == (0, 3)
+                _meshargs._nx3(bad, "point_mesh_distance", "points", torch.float32)
+        assert _meshargs._nx3(torch.zeros(0, 3), "w", "points", torch.float32).shape == (0, 3)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -360,7 +360,7 @@ def test_view_colors_auto_none_and_an_explicit_tree_agree(monkeypatch):
     built = []
     real = renderer.MeshBVH
     outs = [meshcolor.view_colors(*args, **kw), meshcolor.view_colors(*args, bvh=real(T["verts"], T["faces"]), **kw)]
-    monkeypatch.setattr(meshcolor, "MeshBVH", lambda *a, **k: built.append(1) or real(*a, **k))     # counts 'auto' builds
+    monkeypatch.setattr(renderer, "MeshBVH", lambda *a, **k: built.append(1) or real(*a, **k))      # counts 'auto' builds
     outs.append(meshcolor.view_colors(*args, bvh="auto", **kw))
     assert len(built) == (len(sc["faces"]) >= meshcolor.AUTO_BVH_MIN_FACES)
     monkeypatch.setattr(meshcolor, "AUTO_BVH_MIN_FACES", 1024)

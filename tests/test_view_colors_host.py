@@ -190,7 +190,8 @@ def test_meshcolor_imports_without_cuda_and_leaves_the_pinned_surfaces_alone():
 
 
 def test_meshcolor_rejections_need_no_gpu():
-    from connecting_the_dots_amd import mesh, meshcolor
+    from connecting_the_dots_amd import _meshargs, mesh, meshcolor
+    resolve = lambda *a: _meshargs._resolve_bvh(*a, meshcolor.AUTO_BVH_MIN_FACES)     # noqa: E731  as view_colors calls it
     p, im = torch.zeros(4, 3), torch.zeros(2, 3, 4, 5)
     K, R, t = torch.eye(3), torch.eye(3).repeat(2, 1, 1), torch.zeros(2, 3)
     with pytest.raises(RuntimeError, match="CUDA tensor"):
@@ -230,14 +231,14 @@ def test_meshcolor_rejections_need_no_gpu():
     # the tree: of other tensors, unusable, of a wrong kind, 'auto' below the threshold
     v, f = torch.zeros(5, 3), torch.zeros(2, 3, dtype=torch.int32)
     with pytest.raises(RuntimeError, match="other verts / faces"):
-        meshcolor._resolve_bvh(_fake_bvh(v.clone(), f), v, f, "view_colors")
+        resolve(_fake_bvh(v.clone(), f), v, f, "view_colors")
     for bad in ("bvh", 3, (v, f)):
         with pytest.raises(RuntimeError, match="None, 'auto' or a renderer.MeshBVH"):
-            meshcolor._resolve_bvh(bad, v, f, "view_colors")
+            resolve(bad, v, f, "view_colors")
     good = _fake_bvh(v, f)
-    assert meshcolor._resolve_bvh(good, v, f, "x") is good and meshcolor._resolve_bvh(None, v, f, "x") is None
-    assert meshcolor._resolve_bvh(_fake_bvh(v, f, usable=False), v, f, "x") is None       # falls back to brute force
-    assert meshcolor._resolve_bvh("auto", v, f, "x") is None                               # below the threshold: no build
+    assert resolve(good, v, f, "x") is good and resolve(None, v, f, "x") is None
+    assert resolve(_fake_bvh(v, f, usable=False), v, f, "x") is None       # falls back to brute force
+    assert resolve("auto", v, f, "x") is None                               # below the threshold: no build
     assert isinstance(mesh.TsdfMesh, type)
 
 

@@ -9,7 +9,8 @@ Compiles every csrc/*.hip present in either tree (--only NAME ...: the files of 
 it is at the base and as it is in the working tree, to gfx950 assembly with
 the flags of connecting_the_dots_amd/build.py plus `--cuda-device-only -S` (into a temporary directory, never into the
 tree) and compares per kernel symbol, whichever file defines it:
-  * the set of .amdhsa_kernel symbols (each exactly once on either side);
+  * the set of .amdhsa_kernel symbols (one that several files define -- a kernel in a header, with internal linkage or
+    as a template -- counts once per file, as symbol@file, and is compared file by file);
   * the instruction stream from the kernel's label to its .Lfunc_end, and its .amdhsa_* descriptor block (register
     counts, LDS, scratch, ...), textually, after renumbering the function-local labels (.LBB<function>_<block>,
     .Lfunc_end<function>) and dropping comments.
@@ -79,13 +80,11 @@ def kernels_of(path):
 
 
 def collect(paths):
-    merged, dup = {}, []
+    per_name = {}
     for p in paths:
         for name, k in kernels_of(p).items():
-            if name in merged:
-                dup.append(name)
-            merged[name] = k + (os.path.basename(p),)
-    return merged, dup
+            per_name.setdefault(name, []).append(k + (os.path.basename(p),))
+    return {name if len(ks) == 1 else "%s@%s" % (name, k[2]): k for name, ks in per_name.items() for k in ks}
 
 
 def main():
@@ -111,8 +110,8 @@ def main():
             if unknown:
                 ap.error("no such csrc file in either tree: " + ", ".join(sorted(unknown)))
             family = sorted(args.only)
-        old, dup_old = collect(compile_family(base_tree, family, os.path.join(tmp, "base"), args.extra))
-        new, dup_new = collect(compile_family(ROOT, family, os.path.join(tmp, "new"), args.extra))
+        old = collect(compile_family(base_tree, family, os.path.join(tmp, "base"), args.extra))
+        new = collect(compile_family(ROOT, family, os.path.join(tmp, "new"), args.extra))
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
@@ -125,9 +124,6 @@ def main():
                 print("DIFFERENT %s: %s (%s -> %s)" % (what, name, old[name][2], new[name][2]))
                 for s in list(difflib.unified_diff(a, b, lineterm="", n=0))[2:2 + args.show]:
                     print("    " + s)
-    for name in dup_old + dup_new:
-        print("DEFINED IN TWO FILES: " + name)
-        bad += 1
 
     def scratch(ks):
         n = [int(s.split()[-1]) for k in ks.values() for s in k[1] if s.startswith(".amdhsa_private_segment_fixed_size")]

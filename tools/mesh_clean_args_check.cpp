@@ -5,17 +5,10 @@
 //         -Xarch_host -fno-sanitize-recover=undefined connecting_the_dots_amd/csrc/mesh_clean.hip \
 //         tools/mesh_clean_args_check.cpp -o tools/bin/mesh_clean_args_check && tools/bin/mesh_clean_args_check
 // Prints "ok: 0 failures" and exits 0; a sanitizer report or a wrong status code fails it.
-#include <cstdio>
-#include <cstdlib>
-#include <cstdint>
-#include <vector>
 #include "../include/ctd_hip_mesh_clean.h"
-static int fails = 0;
-#define EXPECT(expr, want) do { int got_ = (expr); if (got_ != (want)) { ++fails; std::printf("line %d: got %d want %d\n", __LINE__, got_, (want)); } } while (0)
+#include "args_check.h"
 int main() {
-  std::vector<char> raw(8192 * 8 + 256);
-  char* base = (char*)(((uintptr_t)raw.data() + 255) / 256 * 256);
-  auto P = [&](int i) { return base + 8192 * i; };
+  const Arena P(8192, 8);
   int32_t *faces = (int32_t*)P(0), *fo = (int32_t*)P(2), *fi = (int32_t*)P(3), *vi = (int32_t*)P(4), *label = (int32_t*)P(2), *size = (int32_t*)P(3);
   float* verts = (float*)P(1);
   int64_t* counts = (int64_t*)P(5);
@@ -78,6 +71,5 @@ int main() {
   EXPECT(ctd_mesh_components_i32(faces, verts, n, m, 1, label, size, ncomp, ws, nws - 1, -1, nullptr), 2);
   EXPECT(ctd_mesh_components_i32(faces, verts, n, m, 1, label, size, ncomp, (char*)ws + 128, nws, -1, nullptr), 2);
   EXPECT(ctd_mesh_components_i32(faces, verts, 0, 0, 0, label, size, ncomp, nullptr, 0, -1, nullptr), 2);
-  std::printf("%s: %d failures\n", fails ? "FAILED" : "ok", fails);
-  return fails != 0;
+  return report();
 }

@@ -5,14 +5,8 @@
 //         -Xarch_host -fno-sanitize-recover=undefined connecting_the_dots_amd/csrc/mesh_color.hip \
 //         tools/mesh_color_args_check.cpp -o tools/bin/mesh_color_args_check && tools/bin/mesh_color_args_check
 // Prints "ok: 0 failures" and exits 0; a sanitizer report or a wrong status code fails it.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 #include "../include/ctd_hip_mesh_color.h"
-static int fails = 0;
-#define EXPECT(expr, want) do { int got_ = (expr); if (got_ != (want)) { ++fails; std::printf("line %d: got %d want %d\n", __LINE__, got_, (want)); } } while (0)
+#include "args_check.h"
 
 struct Args {
   float *points, *normals, *images, *K, *R, *t, *verts, *color, *weight;
@@ -28,9 +22,7 @@ struct Args {
 };
 
 int main() {
-  std::vector<char> raw(4096 * 15 + 256);
-  char* base = (char*)(((uintptr_t)raw.data() + 255) / 256 * 256);
-  auto P = [&](int i) { return base + 4096 * i; };
+  const Arena P(4096, 15);
   Args a;
   a.points = (float*)P(0); a.normals = (float*)P(1); a.images = (float*)P(2); a.valid = (uint8_t*)P(3); a.K = (float*)P(4);
   a.R = (float*)P(5); a.t = (float*)P(6); a.verts = (float*)P(7); a.faces = (int32_t*)P(8); a.bvh = P(9);
@@ -98,6 +90,5 @@ int main() {
   b = a; b.n = 0; b.bvh = nullptr; b.flags = nullptr; b.normals = nullptr; b.valid = nullptr; EXPECT(b.call(), 0);
   b = a; b.n = 0; b.nf = 0; b.points = b.images = b.K = b.R = b.t = b.color = b.weight = b.verts = nullptr; b.n_views = nullptr;
   b.faces = nullptr; EXPECT(b.call(), 0);
-  std::printf("%s: %d failures\n", fails ? "FAILED" : "ok", fails);
-  return fails != 0;
+  return report();
 }

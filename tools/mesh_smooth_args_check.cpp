@@ -6,19 +6,10 @@
 //         -Xarch_host -fno-sanitize-recover=undefined connecting_the_dots_amd/csrc/mesh_smooth.hip \
 //         tools/mesh_smooth_args_check.cpp -o tools/bin/mesh_smooth_args_check && tools/bin/mesh_smooth_args_check
 // Prints "ok: 0 failures" and exits 0; a sanitizer report or a wrong status code fails it.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstdint>
-#include <vector>
 #include "../include/ctd_hip_mesh_smooth.h"
-static int fails = 0;
-#define EXPECT(expr, want) do { int got_ = (expr); if (got_ != (want)) { ++fails; std::printf("line %d: got %d want %d\n", __LINE__, got_, (want)); } } while (0)
+#include "args_check.h"
 int main() {
-  const size_t slot = 16384;
-  std::vector<char> raw(slot * 9 + 256);
-  char* base = (char*)(((uintptr_t)raw.data() + 255) / 256 * 256);
-  auto P = [&](int i) { return base + slot * i; };
+  const Arena P(16384, 9);
   int32_t *faces = (int32_t*)P(0), *off = (int32_t*)P(1), *nb = (int32_t*)P(2), *fo = (int32_t*)P(3), *fi = (int32_t*)P(4);
   uint8_t* fl = (uint8_t*)P(5);
   int64_t* counts = (int64_t*)P(6);
@@ -119,6 +110,5 @@ int main() {
   EXPECT(ctd_mesh_vertex_normals_f32(verts, n, (int32_t*)P(1), m, fo, fi, ninc, (float*)fo + n, -1, nullptr), 1);
   EXPECT(ctd_mesh_vertex_normals_f32(verts, n, (int32_t*)P(1), m, fo, fi, ninc, (float*)fi + ninc - 1, -1, nullptr), 1);
   EXPECT(ctd_mesh_vertex_normals_f32(verts, n, (int32_t*)P(1), m, fo, fi, ninc, (float*)P(1) - 3 * n + 1, -1, nullptr), 1);   // ends 4 bytes into faces
-  std::printf("%s: %d failures\n", fails ? "FAILED" : "ok", fails);
-  return fails != 0;
+  return report();
 }

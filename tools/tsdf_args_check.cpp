@@ -5,18 +5,11 @@
 //         -Xarch_host -fno-sanitize-recover=undefined connecting_the_dots_amd/csrc/tsdf.hip tools/tsdf_args_check.cpp \
 //         -o tools/bin/tsdf_args_check && tools/bin/tsdf_args_check
 // Prints "ok: 0 failures" and exits 0; a sanitizer report or a wrong status code fails it.
-#include <cstdio>
-#include <cstdlib>
-#include <cmath>
-#include <cstdint>
-#include <vector>
 #include "../include/ctd_hip_tsdf.h"
-static int fails = 0;
-#define EXPECT(expr, want) do { int got_ = (expr); if (got_ != (want)) { ++fails; std::printf("line %d: got %d want %d\n", __LINE__, got_, (want)); } } while (0)
+#include "args_check.h"
 int main() {
-  std::vector<char> raw(4096 * 12 + 256);
-  char* base = (char*)(((uintptr_t)raw.data() + 255) / 256 * 256);
-  auto P = [&](int i) { return (float*)(base + 4096 * i); };
+  const Arena arena(4096, 12);
+  auto P = [&](int i) { return (float*)arena(i); };
   float *tsdf = P(0), *weight = P(1), *origin = P(2), *depth = P(3), *ray = P(5), *K = P(6), *R = P(7), *t = P(8), *pts = P(9), *nrm = P(10);
   uint8_t* valid = (uint8_t*)P(4);
   int64_t* src = (int64_t*)P(11);
@@ -65,6 +58,5 @@ int main() {
   EXPECT(ctd_tsdf_raycast_f32(tsdf, weight, origin, 0.1f, ray, R, t, 0.5f, 0.05f, 2147483647, 1.f, out, 2147483647, 2048, 2048, 2048, 64, 1 << 24, 1 << 24, -1, nullptr), 3);
   EXPECT(ctd_tsdf_raycast_f32(tsdf, weight, origin, 0.1f, ray, R, t, 0.5f, 0.05f, 8, 1.f, ray + 2, 2, 3, 4, 5, 3, 4, 5, -1, nullptr), 1);
   EXPECT(ctd_tsdf_raycast_f32(tsdf, weight, origin, 0.1f, ray, R, t, 0.f, 0.05f, 1, 1.f, out, 0, 3, 4, 5, 3, 4, 5, -1, nullptr), 0);
-  std::printf("%s: %d failures\n", fails ? "FAILED" : "ok", fails);
-  return fails != 0;
+  return report();
 }
