@@ -20,7 +20,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          against the mesh by brute force or through renderer.MeshBVH, bilinear sample, blend of the views
     meshsmooth           the mesh's connectivity by vertex (include/ctd_hip_mesh_smooth.h): one-rings, incident faces, boundary
                          and non-manifold edges; Taubin smoothing over the one-rings; area-weighted vertex normals
-    _meshargs            what the five mesh modules and renderer share above the C calls: argument checks, the choice of
+    meshsimplify         mesh simplification (include/ctd_hip_mesh_simplify.h): vertex clustering on a uniform grid, every
+                         cluster's vertex at the minimum of its summed plane quadrics, duplicate faces dropped
+    _meshargs            what the six mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """
 from . import torchext  # noqa: F401

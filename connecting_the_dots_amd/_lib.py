@@ -1,6 +1,6 @@
 """ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
 ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h,
-ctd_hip_mesh_dist.h, ctd_hip_mesh_color.h and ctd_hip_mesh_smooth.h).
+ctd_hip_mesh_dist.h, ctd_hip_mesh_color.h, ctd_hip_mesh_smooth.h and ctd_hip_mesh_simplify.h).
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -239,6 +239,15 @@ MESH_SMOOTH_SIGNATURES = {
     "ctd_mesh_vertex_normals_f32": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp]),
 }
 
+# vertex clustering with quadric placement of include/ctd_hip_mesh_simplify.h (an addition beside the headers above;
+# meshsimplify.mesh_simplify, meshsimplify.simplify_tsdf_mesh)
+MESH_SIMPLIFY_SIGNATURES = {
+    "ctd_mesh_simplify_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
+    "ctd_mesh_simplify_f32": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_float, _c_float, _c_float, _c_float,
+                                       ctypes.c_double, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_size_t, _c_int,
+                                       _vp]),
+}
+
 _lib = None
 
 
@@ -256,7 +265,7 @@ def lib():
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
                                   list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
                                   list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()) +
-                                  list(MESH_SMOOTH_SIGNATURES.items())):
+                                  list(MESH_SMOOTH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

@@ -31,6 +31,7 @@
 #include "../../include/ctd_hip_mesh_smooth.h"
 #include "ctd_common.h"
 #include "ctd_compact.h"
+#include "ctd_row_sort.h"
 #include "ctd_validate.h"
 
 namespace ctd {
@@ -156,43 +157,7 @@ __device__ inline void run_tally(int mult, int j, long i, int& deg, int& flags, 
   }
 }
 
-// one lane: r entries `kChunk` apart in LDS, ascending
-__device__ inline void lane_sort(int* col, int r) {
-  for (int k = 1; k < r; ++k) {
-    const int v = col[k * kChunk];
-    int j = k;
-    for (; j > 0 && col[(j - 1) * kChunk] > v; --j) col[j * kChunk] = col[(j - 1) * kChunk];
-    col[j * kChunk] = v;
-  }
-}
-
-// the workgroup: a[0 .. n) in global memory, ascending.  Merges of size k = 2, 4, ...: first the comparators (i, its mirror
-// in the block of k), then distances k/4 .. 1; the smaller value always goes to the smaller index, so values past the end
-// (+infinity in thought) never move and comparators that reach them are skipped.  Ends with a barrier.
-__device__ inline void wg_sort(int* a, int n) {
-  for (long k = 2; (k >> 1) < n; k <<= 1) {
-    const long h = k >> 1, pairs = (n + k - 1) / k * h;        // h comparators in every block of k that starts inside the row
-    for (long t = threadIdx.x; t < pairs; t += kChunk) {
-      const long base = (t / h) * k, off = t % h, i = base + off, p = base + k - 1 - off;
-      if (p < n) {
-        const int x = a[i], y = a[p];
-        if (x > y) { a[i] = y; a[p] = x; }
-      }
-    }
-    __syncthreads();
-    for (long j = h >> 1; j >= 1; j >>= 1) {
-      const long pairs_j = (n + 2 * j - 1) / (2 * j) * j;
-      for (long t = threadIdx.x; t < pairs_j; t += kChunk) {
-        const long i = (t / j) * 2 * j + t % j, p = i + j;
-        if (p < n) {
-          const int x = a[i], y = a[p];
-          if (x > y) { a[i] = y; a[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
+// (lane_sort and wg_sort: ctd_row_sort.h)
 
 __global__ __launch_bounds__(kChunk) void ma_rows_kernel(const int* __restrict__ foff, int* fid, int* raw, int* __restrict__ deg,
                                                          uint8_t* __restrict__ vflags, int* __restrict__ wg_deg, int64_t* counts,
