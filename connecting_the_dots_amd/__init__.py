@@ -22,7 +22,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          and non-manifold edges; Taubin smoothing over the one-rings; area-weighted vertex normals
     meshsimplify         mesh simplification (include/ctd_hip_mesh_simplify.h): vertex clustering on a uniform grid, every
                          cluster's vertex at the minimum of its summed plane quadrics, duplicate faces dropped
-    _meshargs            what the six mesh modules and renderer share above the C calls: argument checks, the choice of
+    meshsdf              signed nearest-face queries (include/ctd_hip_mesh_sdf.h): the side by the angle-weighted pseudonormal,
+                         a distance cutoff, a mesh back into a TSDF volume, the signed error of one mesh against another
+    _meshargs            what the seven mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """
 from . import torchext  # noqa: F401

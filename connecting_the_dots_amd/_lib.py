@@ -248,6 +248,13 @@ MESH_SIMPLIFY_SIGNATURES = {
                                        _vp]),
 }
 
+# signed nearest-face queries of include/ctd_hip_mesh_sdf.h (an addition beside the headers above;
+# meshsdf.point_mesh_signed_distance, meshsdf.mesh_to_tsdf, meshsdf.signed_error)
+MESH_SDF_SIGNATURES = {
+    "ctd_point_mesh_signed_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _c_i64, _vp, _c_float, _vp, _vp, _vp,
+                                           _vp, _vp, _c_int, _vp]),
+}
+
 _lib = None
 
 
@@ -265,7 +272,8 @@ def lib():
                                   list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
                                   list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
                                   list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()) +
-                                  list(MESH_SMOOTH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items())):
+                                  list(MESH_SMOOTH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) +
+                                  list(MESH_SDF_SIGNATURES.items())):
             fn = getattr(l, name)       # AttributeError here means header / library mismatch
             fn.restype = res
             fn.argtypes = args

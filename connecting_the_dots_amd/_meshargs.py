@@ -1,4 +1,4 @@
-"""What the mesh modules (meshops, mesheval, meshcolor, meshsmooth, meshsimplify) and the renderer share above the C calls: the checks
+"""What the mesh modules (meshops, mesheval, meshcolor, meshsmooth, meshsimplify, meshsdf) and the renderer share above the C calls: the checks
 of [rows,3] tensors and of flags, the choice of a tree for a query and the call that falls back from it, and the steps
 every `*_tsdf_mesh` function takes.  Private: the public names stay in the modules that use these."""
 import torch

@@ -11,6 +11,8 @@
 // ab = b - a, ac = c - a as computed, after the clamp 0 <= s <= 1, 0 <= t <= 1 - s (each clamp a comparison that a NaN
 // fails, so a NaN parameter becomes 0): whatever rounding did to the region tests, q is a convex combination of a,
 // a + ab and a + ac up to the rounding of that one expression.  point_mesh.hip derives its pruning bound from this.
+// `region` records the branch that was taken, for the signed query (include/ctd_hip_mesh_sdf.h), which must not
+// reclassify from the clamped parameters; a caller that ignores it pays nothing, and d2 and q do not depend on it.
 #pragma once
 
 #include "ctd_common.h"
@@ -20,6 +22,7 @@ namespace ctd {
 struct PointTri {
   float d2;
   float q[3];
+  int region;   // the branch taken: 0, 1, 2 vertex a, b, c; 3, 4, 5 edge ab, ac, bc; 6 the interior
 };
 
 __host__ __device__ inline float pt_dot(const float* u, const float* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
@@ -42,21 +45,28 @@ __host__ __device__ inline PointTri point_tri(const float* p, const float* a, co
   float s = 0.f, t = 0.f;
   if (d1 <= 0.f && d2 <= 0.f) {
     vertex = 0;
+    r.region = 0;
   } else if (d3 >= 0.f && d4 <= d3) {
     vertex = 1;
+    r.region = 1;
   } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
     s = d1 / (d1 - d3);
+    r.region = 3;
   } else if (d6 >= 0.f && d5 <= d6) {
     vertex = 2;
+    r.region = 2;
   } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
     t = d2 / (d2 - d6);
+    r.region = 4;
   } else if (va <= 0.f && e43 >= 0.f && e56 >= 0.f) {
     t = e43 / (e43 + e56);
     s = 1.f - t;
+    r.region = 5;
   } else {
     const float inv = 1.f / ((va + vb) + vc);
     s = vb * inv;
     t = vc * inv;
+    r.region = 6;
   }
   s = s > 0.f ? s : 0.f;
   s = s < 1.f ? s : 1.f;
