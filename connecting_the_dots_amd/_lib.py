@@ -1,6 +1,4 @@
-"""ctypes binding of libctd_hip.so (the C ABI of include/ctd_hip.h, ctd_hip_bench.h, ctd_hip_band.h,
-ctd_hip_warp.h, ctd_hip_band_validity.h, ctd_hip_icp.h, ctd_hip_tsdf.h, ctd_hip_mesh.h, ctd_hip_mesh_clean.h,
-ctd_hip_mesh_dist.h, ctd_hip_mesh_color.h, ctd_hip_mesh_smooth.h and ctd_hip_mesh_simplify.h).
+"""ctypes binding of libctd_hip.so: the C ABI of the headers under include/, one table of TABLES per header.
 
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -12,6 +10,7 @@ LIB_PATH = os.path.join(_PKG, "libctd_hip.so")
 
 _c_int, _c_long, _c_float, _c_size_t, _vp = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_size_t,
                                              ctypes.c_void_p)
+_c_i64 = ctypes.c_int64
 
 class PatternLevel(ctypes.Structure):
     """ctd_pattern_level of include/ctd_hip.h"""
@@ -42,8 +41,13 @@ class HdTrainOut(ctypes.Structure):
     _fields_ = [("nodes", _vp), ("roots", _vp), ("leaf_off", _vp), ("leaf_sum", _vp), ("entries", _vp), ("used", _vp),
                 ("cap_nodes", ctypes.c_int64), ("cap_leaves", ctypes.c_int64), ("cap_entries", ctypes.c_int64)]
 
-# name -> (restype, argtypes); mirrors include/ctd_hip.h one to one
-SIGNATURES = {
+# header under include/ -> {name: (restype, argtypes)}, one entry per prototype of that header and in the order in which
+# the headers were added; lib() binds every table, tests/test_abi_and_host.py holds each against its header
+TABLES = {}
+
+# mirrors include/ctd_hip.h one to one.  SIGNATURES stays as the name of this one table, the drop-in interface: the host
+# answers recorded in tests/abi_rejections.py and the per-op host tests look its entry points up under that name
+SIGNATURES = TABLES["ctd_hip.h"] = {
     "ctd_version": (_c_int, []),
     "ctd_status_string": (ctypes.c_char_p, [_c_int]),
     "ctd_xcorrvol_workspace_bytes": (_c_size_t, [_c_int] * 7),
@@ -142,13 +146,13 @@ SIGNATURES = {
 }
 
 # measurement hooks of include/ctd_hip_bench.h (bench.py, tools/): not part of the drop-in interface
-BENCH_SIGNATURES = {
+TABLES["ctd_hip_bench.h"] = {
     "ctd_kernel_timing_enable": (None, [_c_int]),
     "ctd_kernel_timing_collect": (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_int)]),
 }
 
 # band-limited matching of include/ctd_hip_band.h (an addition beside ctd_hip.h; torchext.xcorrvol_argmax_band, ...)
-BAND_SIGNATURES = {
+TABLES["ctd_hip_band.h"] = {
     "ctd_xcorrvol_argmax_band_workspace_bytes": (_c_size_t, [_c_int] * 6),
     "ctd_xcorrvol_argmax_band_f32": (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_vp, _c_size_t,
                                                                                                   _c_int, _vp]),
@@ -158,7 +162,7 @@ BAND_SIGNATURES = {
 
 # forward depth warping and the windowed band of include/ctd_hip_warp.h (an addition beside ctd_hip.h and ctd_hip_band.h;
 # torchext.depth_warp, torchext.disparity_band_window)
-WARP_SIGNATURES = {
+TABLES["ctd_hip_warp.h"] = {
     "ctd_depth_warp_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "ctd_depth_warp_f32": (_c_int, [_vp] * 8 + [_c_int, _vp, _vp] + [_c_int] * 4 + [_vp, _c_size_t, _c_int, _vp]),
     "ctd_disparity_band_window_f32": (_c_int, [_vp, _c_float, _c_int, _c_int, _c_int, _vp, _vp] + [_c_int] * 3 +
@@ -167,7 +171,7 @@ WARP_SIGNATURES = {
 
 # match validity of the band matchers of include/ctd_hip_band_validity.h (an addition beside the headers above;
 # torchext.xcorrvol_band_validity, torchext.costvol_band_validity)
-BAND_VALIDITY_SIGNATURES = {
+TABLES["ctd_hip_band_validity.h"] = {
     "ctd_xcorrvol_band_validity_f32": (_c_int, [_vp, _vp, _c_long] + [_vp] * 7 + [_c_int] * 6 + [_c_float, _c_int, _vp,
                                                                                              _c_size_t, _c_int, _vp]),
     "ctd_costvol_band_validity_f32": (_c_int, [_vp, _vp, _c_long] + [_vp] * 7 + [_c_int] * 6 + [_c_float, _c_int,
@@ -176,7 +180,7 @@ BAND_VALIDITY_SIGNATURES = {
 
 # depth-map normals and point-to-plane ICP of include/ctd_hip_icp.h (an addition beside the headers above;
 # torchext.depth_normals, torchext.depth_icp_system, torchext.depth_icp_update, torchext.depth_icp)
-ICP_SIGNATURES = {
+TABLES["ctd_hip_icp.h"] = {
     "ctd_depth_normals_f32": (_c_int, [_vp] * 3 + [_c_float, _vp] + [_c_int] * 4 + [_c_int, _vp]),
     "ctd_depth_icp_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "ctd_depth_icp_system_f32": (_c_int, [_vp] * 8 + [_c_float] + [_vp] * 3 + [_c_int] * 4 + [_vp, _c_size_t, _c_int, _vp]),
@@ -186,7 +190,7 @@ ICP_SIGNATURES = {
 
 # truncated signed distance volumes of include/ctd_hip_tsdf.h (an addition beside the headers above;
 # torchext.tsdf_volume, torchext.tsdf_integrate, torchext.tsdf_surface_points, torchext.tsdf_raycast)
-TSDF_SIGNATURES = {
+TABLES["ctd_hip_tsdf.h"] = {
     "ctd_tsdf_integrate_f32": (_c_int, [_vp] * 3 + [_c_float] + [_vp] * 6 + [_c_float, _c_float] + [_c_int] * 7 + [_c_int, _vp]),
     "ctd_tsdf_surface_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "ctd_tsdf_surface_points_f32": (_c_int, [_vp] * 3 + [_c_float, _c_float] + [_vp] * 4 + [ctypes.c_int64] + [_c_int] * 4 +
@@ -196,7 +200,7 @@ TSDF_SIGNATURES = {
 }
 
 # marching cubes over a volume of include/ctd_hip_mesh.h (an addition beside the headers above; mesh.tsdf_mesh)
-MESH_SIGNATURES = {
+TABLES["ctd_hip_mesh.h"] = {
     "ctd_tsdf_mesh_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "ctd_tsdf_mesh_faces_i32": (_c_int, [_vp, _vp, _c_float, _vp, _vp, ctypes.c_int64] + [_c_int] * 4 + [_vp, _c_size_t, _c_int,
                                                                                                     _vp]),
@@ -205,8 +209,7 @@ MESH_SIGNATURES = {
 
 # mesh clean-up of include/ctd_hip_mesh_clean.h (an addition beside the headers above; meshops.mesh_components,
 # meshops.mesh_clean, meshops.clean_tsdf_mesh)
-_c_i64 = ctypes.c_int64
-MESH_CLEAN_SIGNATURES = {
+TABLES["ctd_hip_mesh_clean.h"] = {
     "ctd_mesh_clean_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "ctd_mesh_components_i32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _c_size_t, _c_int, _vp]),
     "ctd_mesh_clean_i32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp,
@@ -215,13 +218,13 @@ MESH_CLEAN_SIGNATURES = {
 
 # nearest-face queries of include/ctd_hip_mesh_dist.h (an addition beside the headers above; mesheval.point_mesh_distance,
 # mesheval.reconstruction_error)
-MESH_DIST_SIGNATURES = {
+TABLES["ctd_hip_mesh_dist.h"] = {
     "ctd_point_mesh_distance_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
 }
 
 # colours for mesh points from a track's views of include/ctd_hip_mesh_color.h (an addition beside the headers above;
 # meshcolor.view_colors, meshcolor.color_tsdf_mesh)
-MESH_COLOR_SIGNATURES = {
+TABLES["ctd_hip_mesh_color.h"] = {
     "ctd_mesh_view_colors_f32": (_c_int, [_vp, _vp, _c_int] + [_vp] * 5 + [_c_int] * 4 + [_vp, _c_int, _vp, _c_int, _vp,
                                                                                        _c_float, _c_float, _c_int] +
                                  [_vp] * 4 + [_c_int, _vp]),
@@ -229,7 +232,7 @@ MESH_COLOR_SIGNATURES = {
 
 # connectivity by vertex, Taubin smoothing and vertex normals of include/ctd_hip_mesh_smooth.h (an addition beside the
 # headers above; meshsmooth.MeshAdjacency, meshsmooth.mesh_smooth, meshsmooth.vertex_normals, meshsmooth.smooth_tsdf_mesh)
-MESH_SMOOTH_SIGNATURES = {
+TABLES["ctd_hip_mesh_smooth.h"] = {
     "ctd_mesh_adjacency_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "ctd_mesh_adjacency_i32": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_size_t, _c_int,
                                         _vp]),
@@ -241,7 +244,7 @@ MESH_SMOOTH_SIGNATURES = {
 
 # vertex clustering with quadric placement of include/ctd_hip_mesh_simplify.h (an addition beside the headers above;
 # meshsimplify.mesh_simplify, meshsimplify.simplify_tsdf_mesh)
-MESH_SIMPLIFY_SIGNATURES = {
+TABLES["ctd_hip_mesh_simplify.h"] = {
     "ctd_mesh_simplify_workspace_bytes": (_c_size_t, [_c_i64, _c_i64]),
     "ctd_mesh_simplify_f32": (_c_int, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _c_float, _c_float, _c_float, _c_float,
                                        ctypes.c_double, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_size_t, _c_int,
@@ -250,7 +253,7 @@ MESH_SIMPLIFY_SIGNATURES = {
 
 # signed nearest-face queries of include/ctd_hip_mesh_sdf.h (an addition beside the headers above;
 # meshsdf.point_mesh_signed_distance, meshsdf.mesh_to_tsdf, meshsdf.signed_error)
-MESH_SDF_SIGNATURES = {
+TABLES["ctd_hip_mesh_sdf.h"] = {
     "ctd_point_mesh_signed_f32": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _c_i64, _vp, _c_float, _vp, _vp, _vp,
                                            _vp, _vp, _c_int, _vp]),
 }
@@ -267,16 +270,11 @@ def lib():
                 "connecting_the_dots_amd: %s is missing -- build it with "
                 "`python -m connecting_the_dots_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (list(SIGNATURES.items()) + list(BENCH_SIGNATURES.items()) + list(BAND_SIGNATURES.items()) +
-                                  list(WARP_SIGNATURES.items()) + list(BAND_VALIDITY_SIGNATURES.items()) +
-                                  list(ICP_SIGNATURES.items()) + list(TSDF_SIGNATURES.items()) +
-                                  list(MESH_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) +
-                                  list(MESH_DIST_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()) +
-                                  list(MESH_SMOOTH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) +
-                                  list(MESH_SDF_SIGNATURES.items())):
-            fn = getattr(l, name)       # AttributeError here means header / library mismatch
-            fn.restype = res
-            fn.argtypes = args
+        for table in TABLES.values():
+            for name, (res, args) in table.items():
+                fn = getattr(l, name)       # AttributeError here means header / library mismatch
+                fn.restype = res
+                fn.argtypes = args
         _lib = l
     return _lib
 

@@ -1,20 +1,15 @@
 """CPU-only checks of band-limited matching (include/ctd_hip_band.h: ctd_xcorrvol_argmax_band_f32,
-ctd_costvol_argmin_band_f32): the header against its ctypes table and the built library, argument validation before any
-HIP call and its precedence, the workspace query, `disparity_band` on CPU tensors and the restatement tests/band_ref.py
-on a hand-written volume."""
+ctd_costvol_argmin_band_f32): argument validation before any HIP call and its precedence, the workspace query,
+`disparity_band` on CPU tensors and the restatement tests/band_ref.py on a hand-written volume.  (The header against its
+ctypes table and the built library: tests/test_abi_and_host.py.)"""
 import ctypes
 import inspect
 import math
-import os
 
 import pytest
 import torch
 
 from tests.band_ref import band_ref
-from tests.test_abi_and_host import HEADER, declared_symbols
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAND_HEADER = os.path.join(ROOT, "include", "ctd_hip_band.h")
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 PREPARED = 0x100
@@ -27,33 +22,7 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. header == table == exports
-# ---------------------------------------------------------------------------------------------------------------------
-def test_band_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(BAND_HEADER)
-    assert names == sorted(_lib.BAND_SIGNATURES)
-    assert names == ["ctd_costvol_argmin_band_f32", "ctd_xcorrvol_argmax_band_f32",
-                     "ctd_xcorrvol_argmax_band_workspace_bytes"]
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.BAND_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-
-
-def test_main_header_is_unchanged_by_the_band_header():
-    from connecting_the_dots_amd import _lib
-    main = declared_symbols(HEADER)
-    assert main == sorted(_lib.SIGNATURES)
-    assert not set(main) & set(declared_symbols(BAND_HEADER))
-    assert "ctd_hip_band.h" not in open(HEADER).read()
-    assert not set(_lib.SIGNATURES) & set(_lib.BAND_SIGNATURES)
-    assert _lib.lib().ctd_version() == 5
-
-
-# ---------------------------------------------------------------------------------------------------------------------
+# 1. header == table == exports: tests/test_abi_and_host.py, for every header
 # 2. validation
 # ---------------------------------------------------------------------------------------------------------------------
 class _Buf:

@@ -1,6 +1,6 @@
 """CPU-only checks of the band matchers' validity (include/ctd_hip_band_validity.h: ctd_xcorrvol_band_validity_f32,
-ctd_costvol_band_validity_f32): the header against its ctypes table and the built library, the other headers untouched,
-argument validation before any HIP call and its precedence, the Python surface, and the restatement
+ctd_costvol_band_validity_f32): the definition's sentences (the header against its ctypes table and the built library:
+tests/test_abi_and_host.py), argument validation before any HIP call and its precedence, the Python surface, and the restatement
 tests/band_validity_ref.py against its element-by-element twin and, with the full band, against tests/validity_ref.py."""
 import ctypes
 import inspect
@@ -13,13 +13,9 @@ import torch
 from tests import band_validity_ref as bvr
 from tests import validity_ref as vr
 from tests.band_ref import band_ref
-from tests.test_abi_and_host import HEADER, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAND_HEADER = os.path.join(ROOT, "include", "ctd_hip_band.h")
-WARP_HEADER = os.path.join(ROOT, "include", "ctd_hip_warp.h")
 BV_HEADER = os.path.join(ROOT, "include", "ctd_hip_band_validity.h")
-NAMES = ["ctd_costvol_band_validity_f32", "ctd_xcorrvol_band_validity_f32"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 PREPARED = 0x100
@@ -33,38 +29,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. header == table == exports; the other headers untouched
+# 1. the header (header == table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_band_validity_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(BV_HEADER)
-    assert names == sorted(_lib.BAND_VALIDITY_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.BAND_VALIDITY_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert len(_lib.BAND_VALIDITY_SIGNATURES["ctd_xcorrvol_band_validity_f32"][1]) == 22
-    assert len(_lib.BAND_VALIDITY_SIGNATURES["ctd_costvol_band_validity_f32"][1]) == 21
-
-
-def test_the_other_headers_are_unchanged_by_the_band_validity_header():
-    from connecting_the_dots_amd import _lib
-    main, band, warp = declared_symbols(HEADER), declared_symbols(BAND_HEADER), declared_symbols(WARP_HEADER)
-    assert main == sorted(_lib.SIGNATURES) and band == sorted(_lib.BAND_SIGNATURES) and warp == sorted(_lib.WARP_SIGNATURES)
-    assert band == ["ctd_costvol_argmin_band_f32", "ctd_xcorrvol_argmax_band_f32", "ctd_xcorrvol_argmax_band_workspace_bytes"]
-    assert not set(NAMES) & (set(main) | set(band) | set(warp))
-    assert not set(_lib.BAND_VALIDITY_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) |
-                                                     set(_lib.WARP_SIGNATURES) | set(_lib.BENCH_SIGNATURES))
-    for h in (HEADER, BAND_HEADER, WARP_HEADER):
-        text = open(h).read()
-        assert "ctd_hip_band_validity.h" not in text
-        for n in NAMES:
-            assert n not in text
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_definition():
     text = " ".join(open(BV_HEADER).read().replace("*", " ").split())
     for phrase in ("Pixel (f,h,w) holds disparity d when lo' <= d <= hi'",

@@ -1,7 +1,7 @@
 """CPU-only checks of the depth-map normals and the point-to-plane ICP (include/ctd_hip_icp.h: ctd_depth_normals_f32,
 ctd_depth_icp_system_f32, ctd_depth_icp_update_f32; torchext.depth_normals, depth_icp_system, depth_icp_update,
-depth_icp): the header against its ctypes table and the built library, the other headers untouched, argument validation
-before any HIP call and its precedence, the workspace query, the Python surface, and the restatement tests/icp_ref.py
+depth_icp): the rules' sentences (the header against its ctypes table and the built library: tests/test_abi_and_host.py),
+argument validation before any HIP call and its precedence, the workspace query, the Python surface, and the restatement tests/icp_ref.py
 against the truth of its corner scene: normals, convergence from perturbed poses, what the consistency check says
 before and after, and the two degenerate scenes.
 
@@ -40,13 +40,9 @@ import torch
 
 from tests import fusion_ref as fr
 from tests import icp_ref as ir
-from tests.test_abi_and_host import HEADER, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in ("ctd_hip_band.h", "ctd_hip_warp.h",
-                                                                       "ctd_hip_band_validity.h", "ctd_hip_bench.h")]
 ICP_HEADER = os.path.join(ROOT, "include", "ctd_hip_icp.h")
-NAMES = ["ctd_depth_icp_system_f32", "ctd_depth_icp_update_f32", "ctd_depth_icp_workspace_bytes", "ctd_depth_normals_f32"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 NAN = float("nan")
@@ -71,38 +67,8 @@ def te():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. header == table == exports; the other headers untouched
+# 1. the header (header == table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_icp_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(ICP_HEADER)
-    assert names == sorted(_lib.ICP_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.ICP_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.ICP_SIGNATURES[n][1]) for n in NAMES] == [20, 14, 4, 11]
-
-
-def test_the_other_headers_are_unchanged_by_the_icp_header():
-    from connecting_the_dots_amd import _lib
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) |
-              set(_lib.BAND_VALIDITY_SIGNATURES) | set(_lib.BENCH_SIGNATURES))
-    assert not set(_lib.ICP_SIGNATURES) & others
-    declared = set()
-    for h in OTHER_HEADERS:
-        text = open(h).read()
-        assert "ctd_hip_icp.h" not in text, h
-        for n in NAMES:
-            assert n not in text, (h, n)
-        declared |= set(declared_symbols(h))
-    assert declared == others and not declared & set(NAMES)
-    assert declared_symbols(HEADER) == sorted(_lib.SIGNATURES)
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rules():
     text = " ".join(open(ICP_HEADER).read().replace("*", " ").split())
     for phrase in ("1 <= x <= W-2 and 1 <= y <= H-2",

@@ -1,12 +1,12 @@
 """CPU-only checks of forward depth warping and the windowed band (include/ctd_hip_warp.h: ctd_depth_warp_f32,
-ctd_disparity_band_window_f32; torchext.depth_warp, disparity_band_window, depth_to_disp): the header against its ctypes
-table and the built library, argument validation before any HIP call and its precedence, the workspace query, the Python
-surface's own errors, `depth_to_disp` pinned by hand, and the restatements of tests/warp_ref.py -- on hand-written
-inputs, against `disparity_band`, and for the two properties that make a warped prior worth having."""
+ctd_disparity_band_window_f32; torchext.depth_warp, disparity_band_window, depth_to_disp): argument validation before
+any HIP call and its precedence, the workspace query, the Python surface's own errors, `depth_to_disp` pinned by hand,
+and the restatements of tests/warp_ref.py -- on hand-written inputs, against `disparity_band`, and for the two
+properties that make a warped prior worth having.  (The header against its ctypes table and the built library:
+tests/test_abi_and_host.py.)"""
 import ctypes
 import inspect
 import math
-import os
 
 import numpy as np
 import pytest
@@ -14,12 +14,6 @@ import torch
 
 from tests import fusion_ref as fr
 from tests import warp_ref as wr
-from tests.test_abi_and_host import HEADER, declared_symbols
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAND_HEADER = os.path.join(ROOT, "include", "ctd_hip_band.h")
-WARP_HEADER = os.path.join(ROOT, "include", "ctd_hip_warp.h")
-NAMES = ["ctd_depth_warp_f32", "ctd_depth_warp_workspace_bytes", "ctd_disparity_band_window_f32"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 
@@ -37,35 +31,7 @@ def te():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. header == table == exports
-# ---------------------------------------------------------------------------------------------------------------------
-def test_warp_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(WARP_HEADER)
-    assert names == sorted(_lib.WARP_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.WARP_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-
-
-def test_the_other_headers_are_unchanged_by_the_warp_header():
-    from connecting_the_dots_amd import _lib
-    main, band = declared_symbols(HEADER), declared_symbols(BAND_HEADER)
-    assert main == sorted(_lib.SIGNATURES) and band == sorted(_lib.BAND_SIGNATURES)
-    assert not set(NAMES) & (set(main) | set(band))
-    assert not set(_lib.WARP_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.BENCH_SIGNATURES))
-    for h in (HEADER, BAND_HEADER):
-        text = open(h).read()
-        assert "ctd_hip_warp.h" not in text
-        for n in NAMES:
-            assert n not in text
-    assert _lib.lib().ctd_version() == 5
-
-
-# ---------------------------------------------------------------------------------------------------------------------
+# 1. header == table == exports: tests/test_abi_and_host.py, for every header
 # 2. validation
 # ---------------------------------------------------------------------------------------------------------------------
 class _Buf:

@@ -1,5 +1,5 @@
 """CPU-only checks of the mesh clean-up (include/ctd_hip_mesh_clean.h: ctd_mesh_components_i32, ctd_mesh_clean_i32;
-connecting_the_dots_amd.meshops): the header against its ctypes table and the built library, the rule's sentences,
+connecting_the_dots_amd.meshops): the rule's sentences (the header against its ctypes table: tests/test_abi_and_host.py),
 argument validation before any HIP call and its precedence, the workspace query, the Python module, and the restatement
 tests/meshclean_ref.py against hand-made meshes with known answers and against the truth of the fused scenes.
 
@@ -14,7 +14,6 @@ surfaces, tests/tsdf_ref.scene_surface_distance, before -> after; mean distance 
                                2.17 % -> 0.93 %, ratio 0.429; mean distance 4.21e-03 -> 2.92e-03
 Pinned halfway between the measured ratio and 1.  The largest component holds 91.0 %, 92.0 % and 93.2 % of the faces
 (asserted >= 85 %: a scene that has fallen apart would make the ratios meaningless)."""
-import ctypes
 import inspect
 import os
 import subprocess
@@ -27,15 +26,10 @@ import torch
 from tests import mesh_ref as mr
 from tests import meshclean_ref as mcr
 from tests import tsdf_ref as tr
-from tests.test_abi_and_host import HEADER, declared_symbols
 from tests.test_tsdf_host import _Bufs, fused_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLEAN_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_clean.h")
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in ("ctd_hip_band.h", "ctd_hip_warp.h",
-                                                                       "ctd_hip_band_validity.h", "ctd_hip_bench.h",
-                                                                       "ctd_hip_icp.h", "ctd_hip_tsdf.h", "ctd_hip_mesh.h")]
-NAMES = ["ctd_mesh_clean_i32", "ctd_mesh_clean_workspace_bytes", "ctd_mesh_components_i32"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 F = np.float32
@@ -52,28 +46,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_clean_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(CLEAN_HEADER)
-    assert names == sorted(_lib.MESH_CLEAN_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.MESH_CLEAN_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.MESH_CLEAN_SIGNATURES[n][1]) for n in NAMES] == [17, 2, 12]
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES) | set(_lib.MESH_SIGNATURES))
-    assert not set(_lib.MESH_CLEAN_SIGNATURES) & others
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_clean.h" not in text and "ctd_mesh_clean" not in text and "ctd_mesh_components" not in text, h
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(CLEAN_HEADER).read().replace("*", " ").split())
     for phrase in ("Its three indices lie in [0, n_verts)",

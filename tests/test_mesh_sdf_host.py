@@ -1,6 +1,6 @@
 """CPU-only checks of the signed nearest-face query (include/ctd_hip_mesh_sdf.h: ctd_point_mesh_signed_f32;
-connecting_the_dots_amd.meshsdf): the header against its ctypes table and the built library, argument validation before
-any HIP call, the restatement tests/meshsdf_ref.py against tests/pointmesh_ref.py (bit for bit without a cutoff), and its
+connecting_the_dots_amd.meshsdf): the rule's sentences (header against ctypes table: tests/test_abi_and_host.py), argument
+validation before any HIP call, the restatement tests/meshsdf_ref.py against tests/pointmesh_ref.py (bit for bit without a cutoff), and its
 signs against geometry on four outward-oriented fixtures: a cube (the analytic box distance), a thin wedge (half-spaces; the
 fixture on which the nearest face's own normal is wrong for more than a quarter of the points), an icosphere and a torus.
 
@@ -10,7 +10,6 @@ Measured with the restatement (numpy; the kernels have to give these bits, tests
                         gets 1683 wrong; smallest |dot| / S 0.006
   icosphere(2), 3000:   0 mismatches outside the shell between the inscribed radius and 1; smallest |dot| / S 0.97
   torus(24, 12), 3000:  0 mismatches outside the faceting's margin"""
-import ctypes
 import os
 
 import numpy as np
@@ -20,15 +19,11 @@ import torch
 from tests import bvh_scenes
 from tests import meshsdf_ref as sr
 from tests import pointmesh_ref as pr
-from tests.test_abi_and_host import declared_symbols
 from tests.test_point_mesh_gpu import brute_mesh, brute_points
 from tests.test_tsdf_host import _Bufs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SDF_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_sdf.h")
-OTHER_HEADERS = sorted(os.path.join(ROOT, "include", h) for h in os.listdir(os.path.join(ROOT, "include"))
-                       if h.endswith(".h") and h != "ctd_hip_mesh_sdf.h")
-NAME = "ctd_point_mesh_signed_f32"
 OK, INVALID_ARG = 0, 1
 F = np.float32
 INF = float("inf")
@@ -51,29 +46,8 @@ def same_bits(a, b):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table, the library
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    assert declared_symbols(SDF_HEADER) == sorted(_lib.MESH_SDF_SIGNATURES) == [NAME]
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NAME), "libctd_hip.so does not export %s" % NAME
-    res, args = _lib.MESH_SDF_SIGNATURES[NAME]
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == args and fn.restype == res and len(args) == 18
-    assert args[8] is ctypes.c_int64 and args[10] is ctypes.c_float                      # n_incident, max_d2
-    others = set()
-    for table in ("SIGNATURES", "BAND_SIGNATURES", "WARP_SIGNATURES", "BAND_VALIDITY_SIGNATURES", "BENCH_SIGNATURES",
-                  "ICP_SIGNATURES", "TSDF_SIGNATURES", "MESH_SIGNATURES", "MESH_CLEAN_SIGNATURES", "MESH_DIST_SIGNATURES",
-                  "MESH_COLOR_SIGNATURES", "MESH_SMOOTH_SIGNATURES", "MESH_SIMPLIFY_SIGNATURES"):
-        others |= set(getattr(_lib, table))
-    assert NAME not in others
-    assert len(OTHER_HEADERS) >= 13
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_sdf.h" not in text and "ctd_point_mesh_signed" not in text, h
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(SDF_HEADER).read().replace("*", " ").split())
     for phrase in ("Exactly the rule of ctd_hip_mesh_dist.h: the same point_tri, the same selection, the same skipped faces",

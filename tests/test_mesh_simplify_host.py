@@ -1,5 +1,5 @@
 """CPU-only checks of the mesh simplification (include/ctd_hip_mesh_simplify.h: ctd_mesh_simplify_f32;
-connecting_the_dots_amd.meshsimplify): the header against its ctypes table and the built library, the rule's sentences,
+connecting_the_dots_amd.meshsimplify): the rule's sentences (header against ctypes table: tests/test_abi_and_host.py),
 argument validation before any HIP call and its precedence, the workspace query, the Python module, and the restatement
 tests/meshsimplify_ref.py against hand-made meshes with known answers and against the truth of the fused scenes.
 
@@ -16,7 +16,6 @@ earns its keep at edges and corners (the cube corner below: 4.3e-04 from the cor
 volume: on the noisy unit icosphere (642 vertices, sigma 0.01, default_rng(0)) at a cell of 0.25 from (-1.5, -1.5, -1.5),
 1280 -> 498 faces, 251 vertices, closed, Euler characteristic 2; the volume is 0.9940 of the clean sphere's with quadric
 placement and 0.9665 with mean placement; the rms radial error goes 0.00990 -> 0.01037 (ratio 1.047) | 0.00863 (0.872)."""
-import ctypes
 import inspect
 import os
 import subprocess
@@ -31,14 +30,10 @@ from tests import meshclean_ref as mcr
 from tests import meshsimplify_ref as sr
 from tests import meshsmooth_ref as msr
 from tests import tsdf_ref as tr
-from tests.test_abi_and_host import declared_symbols
 from tests.test_tsdf_host import _Bufs, fused_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIMPLIFY_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_simplify.h")
-OTHER_HEADERS = sorted(os.path.join(ROOT, "include", h) for h in os.listdir(os.path.join(ROOT, "include"))
-                       if h.endswith(".h") and h != "ctd_hip_mesh_simplify.h")
-NAMES = ["ctd_mesh_simplify_f32", "ctd_mesh_simplify_workspace_bytes"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 F = np.float32
@@ -64,43 +59,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_simplify_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(SIMPLIFY_HEADER)
-    assert names == sorted(_lib.MESH_SIMPLIFY_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.MESH_SIMPLIFY_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.MESH_SIMPLIFY_SIGNATURES[n][1]) for n in NAMES] == [25, 2]
-    assert _lib.MESH_SIMPLIFY_SIGNATURES["ctd_mesh_simplify_f32"][1][11] is ctypes.c_double            # reg
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES) | set(_lib.MESH_SIGNATURES) |
-              set(_lib.MESH_CLEAN_SIGNATURES) | set(_lib.MESH_DIST_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES) |
-              set(_lib.MESH_SMOOTH_SIGNATURES))
-    assert not set(_lib.MESH_SIMPLIFY_SIGNATURES) & others
-    assert len(OTHER_HEADERS) >= 12
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_simplify.h" not in text, h
-        for n in NAMES + ["CTD_MESH_SIMPLIFY_"]:
-            assert n not in text, (h, n)
-    text = open(SIMPLIFY_HEADER).read()
-    for h in OTHER_HEADERS:                                        # and it names none of them but the status codes' header
-        if os.path.basename(h) != "ctd_hip.h":
-            assert os.path.basename(h) not in text, h
-    for banned in ("ctd_tsdf", "ctd_mesh_clean", "ctd_mesh_components", "ctd_point_mesh", "ctd_mesh_view_colors", "CTD_MESH_VERT_",
-                   "CTD_MESH_ADJ_MAX_INCIDENT", "ctd_mesh_adjacency", "ctd_mesh_smooth", "ctd_mesh_vertex_normals", "ctd_icp",
-                   "ctd_depth_warp", "ctd_band"):
-        assert banned not in text, banned
-    assert _lib.lib().ctd_version() == 5
-    assert "#define CTD_MESH_SIMPLIFY_MAX_CELLS_PER_AXIS 1048576" in text
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(SIMPLIFY_HEADER).read().replace("*", " ").split())
     for phrase in ("Its three indices lie in [0, n_verts)",
@@ -156,7 +116,8 @@ def test_the_header_states_the_rule():
                    "their order",
                    "No floating-point atomic",
                    "No flag that another workgroup waits on: the same bits on every run",
-                   "it writes every word of the workspace that it reads"):
+                   "it writes every word of the workspace that it reads",
+                   "#define CTD_MESH_SIMPLIFY_MAX_CELLS_PER_AXIS 1048576"):
         assert phrase in text, phrase
 
 

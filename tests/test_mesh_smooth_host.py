@@ -1,6 +1,6 @@
 """CPU-only checks of the mesh connectivity, smoothing and vertex normals (include/ctd_hip_mesh_smooth.h:
-ctd_mesh_adjacency_i32, ctd_mesh_smooth_f32, ctd_mesh_vertex_normals_f32; connecting_the_dots_amd.meshsmooth): the header
-against its ctypes table and the built library, the rule's sentences, argument validation before any HIP call and its
+ctd_mesh_adjacency_i32, ctd_mesh_smooth_f32, ctd_mesh_vertex_normals_f32; connecting_the_dots_amd.meshsmooth): the rule's
+sentences (the header against its ctypes table: tests/test_abi_and_host.py), argument validation before any HIP call and its
 precedence, the workspace queries, the Python module, and the restatement tests/meshsmooth_ref.py against hand-made
 meshes with known answers and against the truth of the fused scenes.
 
@@ -19,7 +19,6 @@ referenced, all 2465 with a finite recomputed normal, 274 of the 2475 gradients 
 for 97.4 % of the vertices that have both; noisy, seed 6: 2500 of 2538 referenced, all finite, 425 gradients not finite,
 dot > 0 for 100 %, > 0.9 for 97.1 %.  (noisy, seed 5, which is not asserted: 2507 referenced, 387 gradients not finite,
 dot > 0 for all but one vertex.)"""
-import ctypes
 import inspect
 import os
 import subprocess
@@ -33,15 +32,10 @@ from tests import mesh_ref as mr
 from tests import meshclean_ref as mcr
 from tests import meshsmooth_ref as msr
 from tests import tsdf_ref as tr
-from tests.test_abi_and_host import HEADER, declared_symbols
 from tests.test_tsdf_host import _Bufs, fused_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOOTH_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_smooth.h")
-OTHER_HEADERS = sorted(os.path.join(ROOT, "include", h) for h in os.listdir(os.path.join(ROOT, "include"))
-                       if h.endswith(".h") and h != "ctd_hip_mesh_smooth.h")
-NAMES = ["ctd_mesh_adjacency_i32", "ctd_mesh_adjacency_workspace_bytes", "ctd_mesh_smooth_f32", "ctd_mesh_smooth_workspace_bytes",
-         "ctd_mesh_vertex_normals_f32"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 F = np.float32
@@ -59,40 +53,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_smooth_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(SMOOTH_HEADER)
-    assert names == sorted(_lib.MESH_SMOOTH_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.MESH_SMOOTH_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.MESH_SMOOTH_SIGNATURES[n][1]) for n in NAMES] == [15, 2, 15, 1, 10]
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES) | set(_lib.MESH_SIGNATURES) |
-              set(_lib.MESH_CLEAN_SIGNATURES) | set(_lib.MESH_DIST_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES))
-    assert not set(_lib.MESH_SMOOTH_SIGNATURES) & others
-    assert HEADER in OTHER_HEADERS and len(OTHER_HEADERS) >= 11
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_smooth.h" not in text, h
-        for n in NAMES + ["CTD_MESH_ADJ_MAX_INCIDENT", "CTD_MESH_VERT_"]:
-            assert n not in text, (h, n)
-    for n in NAMES:
-        for prefix in ("ctd_tsdf", "ctd_mesh_clean", "ctd_mesh_components", "ctd_point_mesh"):
-            assert not n.startswith(prefix)
-        assert "ctd_mesh_view_colors" not in n
-    assert _lib.lib().ctd_version() == 5
-    text = open(SMOOTH_HEADER).read()
-    for define in ("#define CTD_MESH_ADJ_MAX_INCIDENT 1024", "#define CTD_MESH_VERT_REFERENCED 1",
-                   "#define CTD_MESH_VERT_BOUNDARY 2", "#define CTD_MESH_VERT_NONMANIFOLD 4"):
-        assert define in text
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(SMOOTH_HEADER).read().replace("*", " ").split())
     for phrase in ("Its three indices lie in [0, n_verts)",
@@ -136,7 +98,9 @@ def test_the_header_states_the_rule():
                    "every longer row by THE WORKGROUP",
                    "Atomics are integer add, subtract and or only, whose final results do not depend on their order",
                    "No flag that another workgroup waits on: the same bits on every run",
-                   "they write every word of the workspace that they read"):
+                   "they write every word of the workspace that they read",
+                   "#define CTD_MESH_ADJ_MAX_INCIDENT 1024", "#define CTD_MESH_VERT_REFERENCED 1",
+                   "#define CTD_MESH_VERT_BOUNDARY 2", "#define CTD_MESH_VERT_NONMANIFOLD 4"):
         assert phrase in text, phrase
 
 

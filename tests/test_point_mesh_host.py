@@ -1,5 +1,5 @@
 """CPU-only checks of the nearest-face query (include/ctd_hip_mesh_dist.h: ctd_point_mesh_distance_f32;
-connecting_the_dots_amd.mesheval): the header against its ctypes table and the built library, the rule's sentences,
+connecting_the_dots_amd.mesheval): the rule's sentences (the header against its ctypes table: tests/test_abi_and_host.py),
 argument validation before any HIP call, the Python module's own rejections, the restatement tests/pointmesh_ref.py against
 hand-made answers and against the float64 reference tests/chain_scene.mesh_distance, and sample_surface on CPU tensors.
 
@@ -12,7 +12,6 @@ csrc/point_mesh.hip evaluated per point):
 (points uniform in the objects' bounding box grown by 0.5).  The bound is loose because (3) is a worst case over slivers
 and the board's coordinates reach 500 (one ulp there is 3e-5, and the board's eta alone is 9.5e-4); it is derived, not
 tuned.  The float64 run of the same restatement agrees with mesh_distance to 6e-16."""
-import ctypes
 import os
 
 import numpy as np
@@ -21,15 +20,10 @@ import torch
 
 from tests import bvh_scenes, chain_scene
 from tests import pointmesh_ref as pr
-from tests.test_abi_and_host import HEADER, declared_symbols
 from tests.test_tsdf_host import _Bufs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIST_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_dist.h")
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in (
-    "ctd_hip_band.h", "ctd_hip_warp.h", "ctd_hip_band_validity.h", "ctd_hip_bench.h", "ctd_hip_icp.h", "ctd_hip_tsdf.h",
-    "ctd_hip_mesh.h", "ctd_hip_mesh_clean.h")]
-NAME = "ctd_point_mesh_distance_f32"
 OK, INVALID_ARG = 0, 1
 F = np.float32
 
@@ -41,25 +35,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table, the library
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    assert declared_symbols(DIST_HEADER) == sorted(_lib.MESH_DIST_SIGNATURES) == [NAME]
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NAME), "libctd_hip.so does not export %s" % NAME
-    res, args = _lib.MESH_DIST_SIGNATURES[NAME]
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == args and fn.restype == res and len(args) == 12
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES) | set(_lib.MESH_SIGNATURES) |
-              set(_lib.MESH_CLEAN_SIGNATURES))
-    assert NAME not in others
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_dist.h" not in text and "ctd_point_mesh" not in text, h
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(DIST_HEADER).read().replace("*", " ").split())
     for phrase in ("One function computes the distance",

@@ -1,7 +1,7 @@
 """CPU-only checks of the truncated signed distance volumes (include/ctd_hip_tsdf.h: ctd_tsdf_integrate_f32,
 ctd_tsdf_surface_points_f32, ctd_tsdf_raycast_f32; torchext.tsdf_volume, tsdf_integrate, tsdf_surface_points,
-tsdf_raycast): the header against its ctypes table and the built library, the other headers untouched, argument
-validation before any HIP call and its precedence, the workspace query, the Python surface, and the restatement
+tsdf_raycast): the rules' sentences (the header against its ctypes table and the built library:
+tests/test_abi_and_host.py), argument validation before any HIP call and its precedence, the workspace query, the Python surface, and the restatement
 tests/tsdf_ref.py against the truth of its scenes.
 
 Measured on the restatement.  Scenes of tests/fusion_ref.py: B=1, V=4, 48 x 64, a 48^3 grid over 1.6 m around
@@ -47,14 +47,9 @@ import torch
 from tests import fusion_ref as fr
 from tests import icp_ref as ir
 from tests import tsdf_ref as tr
-from tests.test_abi_and_host import HEADER, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in ("ctd_hip_band.h", "ctd_hip_warp.h",
-                                                                       "ctd_hip_band_validity.h", "ctd_hip_bench.h",
-                                                                       "ctd_hip_icp.h")]
 TSDF_HEADER = os.path.join(ROOT, "include", "ctd_hip_tsdf.h")
-NAMES = ["ctd_tsdf_integrate_f32", "ctd_tsdf_raycast_f32", "ctd_tsdf_surface_points_f32", "ctd_tsdf_surface_workspace_bytes"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 NAN, INF = float("nan"), float("inf")
@@ -87,36 +82,8 @@ def te():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. header == table == exports; the other headers untouched
+# 1. the header (header == table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_tsdf_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(TSDF_HEADER)
-    assert names == sorted(_lib.TSDF_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.TSDF_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.TSDF_SIGNATURES[n][1]) for n in NAMES] == [21, 21, 18, 4]
-
-
-def test_the_other_headers_are_unchanged_by_the_tsdf_header():
-    from connecting_the_dots_amd import _lib
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) |
-              set(_lib.BAND_VALIDITY_SIGNATURES) | set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES))
-    assert not set(_lib.TSDF_SIGNATURES) & others
-    declared = set()
-    for h in OTHER_HEADERS:
-        text = open(h).read()
-        assert "ctd_hip_tsdf.h" not in text and "ctd_tsdf" not in text, h
-        declared |= set(declared_symbols(h))
-    assert declared == others
-    assert declared_symbols(HEADER) == sorted(_lib.SIGNATURES)
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rules():
     text = " ".join(open(TSDF_HEADER).read().replace("*", " ").split())
     for phrase in ("X_c = origin[b][c] + voxel (float)index_c",

@@ -1,5 +1,6 @@
 """CPU-only checks of the mesh extraction (include/ctd_hip_mesh.h: ctd_tsdf_mesh_faces_i32, ctd_tsdf_mesh_case;
-connecting_the_dots_amd.mesh): the header against its ctypes table and the built library, the triangle table against
+connecting_the_dots_amd.mesh): the rule's sentences (the header against its ctypes table and the built library:
+tests/test_abi_and_host.py), the triangle table against
 the restatement tests/mesh_ref.py and against its generator, the manifoldness the rule promises, argument validation
 before any HIP call and its precedence, the workspace query, and the Python module (PLY round trip, import without a
 GPU, torchext untouched)."""
@@ -16,17 +17,12 @@ import torch
 
 from tests import mesh_ref as mr
 from tests import tsdf_ref as tr
-from tests.test_abi_and_host import HEADER, declared_symbols
 from tests.test_tsdf_host import _Bufs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MESH_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh.h")
 TABLE_HEADER = os.path.join(ROOT, "connecting_the_dots_amd", "csrc", "ctd_mc_table.h")
 GENERATOR = os.path.join(ROOT, "tools", "make_mc_table.py")
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in ("ctd_hip_band.h", "ctd_hip_warp.h",
-                                                                       "ctd_hip_band_validity.h", "ctd_hip_bench.h",
-                                                                       "ctd_hip_icp.h", "ctd_hip_tsdf.h")]
-NAMES = ["ctd_tsdf_mesh_case", "ctd_tsdf_mesh_faces_i32", "ctd_tsdf_mesh_workspace_bytes"]
 
 OK, INVALID_ARG, WORKSPACE, UNSUPPORTED = 0, 1, 2, 3
 NAN, INF = float("nan"), float("inf")
@@ -46,28 +42,8 @@ def library_case(L, case):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table
+# 1. the header, the table (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_mesh_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    names = declared_symbols(MESH_HEADER)
-    assert names == sorted(_lib.MESH_SIGNATURES) == NAMES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for n in names:
-        assert hasattr(lib, n), "libctd_hip.so does not export %s" % n
-    bound = _lib.lib()
-    for n, (res, args) in _lib.MESH_SIGNATURES.items():
-        assert getattr(bound, n).argtypes == args and getattr(bound, n).restype == res
-    assert [len(_lib.MESH_SIGNATURES[n][1]) for n in NAMES] == [2, 14, 4]
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES))
-    assert not set(_lib.MESH_SIGNATURES) & others
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh.h" not in text and "ctd_tsdf_mesh" not in text, h
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(MESH_HEADER).read().replace("*", " ").split())
     for phrase in ("Cell (i,j,k) of track b exists for i < nx-1, j < ny-1, k < nz-1",

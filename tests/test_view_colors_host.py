@@ -1,5 +1,5 @@
 """CPU-only checks of the view colours (include/ctd_hip_mesh_color.h: ctd_mesh_view_colors_f32;
-connecting_the_dots_amd.meshcolor): the header against its ctypes table and the built library, the rule's sentences,
+connecting_the_dots_amd.meshcolor): the rule's sentences (the header against its ctypes table: tests/test_abi_and_host.py),
 argument validation before any HIP call, the Python module's own rejections and to_uint8 on CPU tensors, the restatement
 tests/viewcolor_ref.py against hand-made answers and against the float64 ray caster of tests/chain_scene.py.
 
@@ -17,7 +17,6 @@ all of whose used views sample their own surface (the 4 x 4 pixels around the fl
 points), the largest |colour - g(X)| of the restatement over both tracks, both modes and the three channels is 8.72e-05
 (track 0; 2.33e-05 on track 1; bilinear interpolation of a curved field under perspective, f32 rounding included);
 COLOR_TOL is four times that."""
-import ctypes
 import functools
 import os
 
@@ -27,15 +26,10 @@ import torch
 
 from tests import chain_scene
 from tests import viewcolor_ref as vr
-from tests.test_abi_and_host import HEADER, declared_symbols
 from tests.test_tsdf_host import _Bufs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COLOR_HEADER = os.path.join(ROOT, "include", "ctd_hip_mesh_color.h")
-OTHER_HEADERS = [HEADER] + [os.path.join(ROOT, "include", h) for h in (
-    "ctd_hip_band.h", "ctd_hip_warp.h", "ctd_hip_band_validity.h", "ctd_hip_bench.h", "ctd_hip_icp.h", "ctd_hip_tsdf.h",
-    "ctd_hip_mesh.h", "ctd_hip_mesh_clean.h", "ctd_hip_mesh_dist.h")]
-NAME = "ctd_mesh_view_colors_f32"
 OK, INVALID_ARG, UNSUPPORTED = 0, 1, 3
 F = np.float32
 NAN, INF = float("nan"), float("inf")
@@ -51,27 +45,8 @@ def L():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 1. the header, the table, the library
+# 1. the header (header == ctypes table == exports: tests/test_abi_and_host.py, for every header)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_table_matches_header_and_library():
-    from connecting_the_dots_amd import _lib
-    assert declared_symbols(COLOR_HEADER) == sorted(_lib.MESH_COLOR_SIGNATURES) == [NAME]
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NAME), "libctd_hip.so does not export %s" % NAME
-    res, args = _lib.MESH_COLOR_SIGNATURES[NAME]
-    fn = getattr(_lib.lib(), NAME)
-    assert fn.argtypes == args and fn.restype == res and len(args) == 26
-    others = (set(_lib.SIGNATURES) | set(_lib.BAND_SIGNATURES) | set(_lib.WARP_SIGNATURES) | set(_lib.BAND_VALIDITY_SIGNATURES) |
-              set(_lib.BENCH_SIGNATURES) | set(_lib.ICP_SIGNATURES) | set(_lib.TSDF_SIGNATURES) | set(_lib.MESH_SIGNATURES) |
-              set(_lib.MESH_CLEAN_SIGNATURES) | set(_lib.MESH_DIST_SIGNATURES))
-    assert NAME not in others
-    for h in OTHER_HEADERS:                                        # no other header includes or declares it
-        text = open(h).read()
-        assert "ctd_hip_mesh_color.h" not in text and "ctd_mesh_view_colors" not in text, h
-    for prefix in ("ctd_tsdf", "ctd_mesh_clean", "ctd_mesh_components", "ctd_point_mesh"):
-        assert not NAME.startswith(prefix)
-    assert _lib.lib().ctd_version() == 5
-
-
 def test_the_header_states_the_rule():
     text = " ".join(open(COLOR_HEADER).read().replace("*", " ").split())
     for phrase in ("Everything is f32 and uncontracted, in the written association, with IEEE division and sqrtf",

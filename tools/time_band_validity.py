@@ -38,7 +38,7 @@ PREPARED = 0x100
 
 def bind(path):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _lib.BAND_SIGNATURES.items():
+    for name, (res, args) in _lib.TABLES["ctd_hip_band.h"].items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
