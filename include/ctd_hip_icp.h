@@ -143,6 +143,10 @@
  *
  * R is not re-orthonormalised.  No workspace.
  *
+ * ok speaks of this call alone.  When system and update are iterated, a view whose last round ends with ok = 0 keeps
+ * whatever pose the earlier rounds (each of which may have had ok = 1) left it with, which can be far from any surface:
+ * such a pose is not to be used.
+ *
  * Errors, before any HIP call, in this order:
  *   CTD_ERR_INVALID_ARG for V < 1, B < 0, V > 64, min_count < 0, a negative or NaN min_pivot or damping, or a NULL
  *     system / R / t / R_out / t_out / ok;

@@ -29,6 +29,34 @@ half a pixel apart when p and q see the same face, and the two views see that fa
 accepts at 0.002 may differ by somewhat more or less than 0.002 in s.  SAME_REL = MAX_REL / 2 and OTHER_REL = 2 * MAX_REL
 bracket the rule's tolerance by a factor of two on either side; `unsure` is asserted to stay below 5 % of the pixels
 of every ordered view pair (measured: tests/test_chain_truth_host.py).
+
+The second half of the chain (tests/test_chain_recon_host.py, tests/test_chain_recon_gpu.py) adds, again from the truth
+alone:
+
+  normal     per pixel the unit normal of the hit face in the camera's frame, R n, turned so that it faces the camera
+             (normal . X_cam < 0); NaN at a miss.
+  recon_grid one volume per track around the truth points of all its views, padded by 4 voxels (the truncation), with
+             one `dims` for both tracks.
+  field      an analytic scalar of the world position with values in [0, 1] and periods of metres; `field_images` holds
+             it at the truth points of every pixel (0 at a miss), so a vertex coloured from the views must come out as
+             `field(vertex)` up to the field's change over the vertex's distance to the truth and over a pixel.
+  occluded64 `occluded64(b, s, points, margin)` casts the ray from the centre of camera s of track b to each point
+             against the true mesh.  With `length` the distance from the centre to the point and `first` the distance
+             to the first hit: occluded when first < length - 2 margin, visible when first >= length - margin / 2
+             (or nothing is hit), grey in between.  The silhouette rule: a point is grey as well when its ray passes
+             within `reach` voxels (a voxel is margin / 2, the README's margin being 2 voxels) of a silhouette of view s
+             that lies in front of it.  A silhouette pixel is a pixel of the view's truth whose 3 x 3 neighbourhood
+             holds two surfaces (surface = triangle // 2) or a miss; z_near is the nearest depth of that neighbourhood,
+             and a voxel there spans f * voxel / z_near pixels.  The ray is near the silhouette when the point's
+             projection (not rounded) lies within reach * f * voxel / z_near pixels of the silhouette pixel's centre,
+             and the silhouette lies in front of the point when z_near < z - 2 margin, z being the point's depth in s:
+             only a surface that far in front makes a point occluded, and an edge nearer to the point's own depth is
+             the rim of the point's own surface or of a neighbour that cannot hide it.  Near an edge in front, a
+             reconstruction eroded or dilated there decides differently from the true mesh without being wrong.
+             Points outside the image are grey.  REACH = 0.5: at a reach of one voxel no truly occluded candidate of the
+             reference chain is used, but 14.7 % of track 0's candidates are grey (its boxes stand a metre from the
+             cameras, where a voxel spans 6 pixels, in front of a wall full of vertices); at half a voxel grey is 9.2 %
+             and 43 of 268 truly occluded candidates are used (tests/test_chain_recon_host.py measures both).
 """
 import functools
 
@@ -239,6 +267,152 @@ def mesh_distance(points, verts, faces, chunk=8192):
         d2 = np.where(inside, h * h, d2)
         out[i:i + chunk] = np.sqrt(d2.min(1))
     return out
+
+
+def mesh_distance_near(points, verts, faces, k=24, chunk=2048):
+    """`mesh_distance` over the k faces whose centroids lie nearest to each point only: an upper bound of the distance,
+    and the distance itself when the nearest face is among them (a mesh of small triangles, such as a TSDF mesh, seen
+    from nearby); float64.  Faces without area count by their edges."""
+    P = np.asarray(points, np.float64).reshape(-1, 3)
+    tri = np.asarray(verts, np.float64)[faces]                          # [f,3,3]
+    cen = tri.mean(1)
+    k = min(k, len(tri))
+    out = np.empty(P.shape[0])
+
+    def seg(p, u, w):
+        e = w - u
+        ee = (e * e).sum(-1)
+        s = np.clip(((p - u) * e).sum(-1) / np.where(ee > 0, ee, 1.0), 0.0, 1.0)
+        d = p - (u + s[..., None] * e)
+        return (d * d).sum(-1)
+
+    for i in range(0, P.shape[0], chunk):
+        p = P[i:i + chunk]
+        d2c = ((p[:, None, :] - cen[None]) ** 2).sum(-1)
+        idx = np.argpartition(d2c, k - 1, axis=1)[:, :k]                # [m,k]
+        a, b, c = (tri[idx, j] for j in range(3))                       # [m,k,3]
+        p = p[:, None, :]
+        n = np.cross(b - a, c - a)
+        nn = (n * n).sum(-1)
+        flat = nn > 0
+        n = n / np.sqrt(np.where(flat, nn, 1.0))[..., None]
+        h = ((p - a) * n).sum(-1)
+        foot = p - h[..., None] * n
+        inside = flat.copy()
+        for u, w in ((a, b), (b, c), (c, a)):
+            inside &= (np.cross(w - u, foot - u) * n).sum(-1) >= 0
+        d2 = np.minimum(np.minimum(seg(p, a, b), seg(p, b, c)), seg(p, c, a))
+        out[i:i + chunk] = np.sqrt(np.where(inside, h * h, d2).min(1))
+    return out
+
+
+def face_normals(mesh):
+    """unit normals [k,3] float64 of a mesh's triangles, (v1 - v0) x (v2 - v0)"""
+    v = np.asarray(mesh["verts"], np.float64)
+    f = mesh["faces"]
+    n = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def truth_normals(sc, b, v):
+    """-> [H,W,3] float64: the normal of the hit face in the frame of camera v of track b, facing the camera; NaN at a miss"""
+    T = sc.truth[b][v]
+    R, t = np.asarray(sc.R[b, v], np.float64), np.asarray(sc.t[b, v], np.float64)
+    n = face_normals(sc.meshes[b])[np.maximum(T["face"], 0)] @ R.T
+    Xc = T["X"] @ R.T + t
+    n = np.where((n * Xc).sum(-1, keepdims=True) > 0, -n, n)
+    return np.where(T["hit"][..., None], n, np.nan)
+
+
+def truth_points(sc, b, mask_key="hit"):
+    """the truth points of the pixels of all views of track b under a mask -> [n,3] float64"""
+    return np.concatenate([sc.truth[b][v]["X"][sc.truth[b][v][mask_key]] for v in range(V)])
+
+
+def recon_grid(voxel, pad=4):
+    """-> (origin f32 [B,3], dims = (nx, ny, nz)): per track the bounding box of its truth points padded by `pad` voxels;
+    dims is the larger of the two tracks' on every axis"""
+    sc = scene()
+    lo = np.stack([truth_points(sc, b).min(0) - pad * voxel for b in range(B)])
+    hi = np.stack([truth_points(sc, b).max(0) + pad * voxel for b in range(B)])
+    dims = tuple(int(n) for n in (np.ceil((hi - lo) / voxel).astype(np.int64) + 1).max(0))
+    return np.ascontiguousarray(lo.astype(np.float32)), dims
+
+
+FIELD_PERIODS = (2.3, 1.7, 3.1)                                   # metres
+FIELD_PHASES = (0.0, 1.0, 2.0)
+
+
+def field(X):
+    """[...,3] world points -> [...] float64 in [0, 1]: 1/2 + the mean of three sines, one per coordinate, / 2"""
+    X = np.asarray(X, np.float64)
+    s = sum(np.sin(2 * np.pi * X[..., c] / FIELD_PERIODS[c] + FIELD_PHASES[c]) for c in range(3))
+    return 0.5 + s / 6.0
+
+
+def field_images(b):
+    """-> f32 [V,1,H,W]: the field at the truth points of track b's views, 0 at a miss"""
+    sc = scene()
+    return np.stack([np.where(T["hit"], field(T["X"]), 0.0)[None] for T in sc.truth[b]]).astype(np.float32)
+
+
+def silhouette_mask(face):
+    """face [H,W] triangle ids -> bool [H,W]: the 3 x 3 neighbourhood (inside the image) holds two surfaces or a miss"""
+    surf = np.where(face >= 0, face // 2, -1)
+    pad = np.pad(surf, 1, mode="edge")
+    out = surf < 0
+    for dy in range(3):
+        for dx in range(3):
+            n = pad[dy:dy + H, dx:dx + W]
+            out |= (n != surf) | (n < 0)
+    return out
+
+
+REACH = 0.5                                                       # of the silhouette rule, in voxels
+
+
+def near_silhouette(T, f_reach, us, vs, z_limit):
+    """the truth T of a view, f_reach = focal length * the reach as a length, projections (us, vs) [n] in pixels and depths
+    z_limit [n] -> bool [n]: the centre of a silhouette pixel whose z_near is below z_limit lies within f_reach / z_near
+    pixels of (us, vs)"""
+    sil = silhouette_mask(T["face"])
+    pad = np.pad(T["z64"], 1, mode="edge")
+    z_near = np.min([pad[dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)], 0)
+    with np.errstate(all="ignore"):
+        radius = np.where(sil & np.isfinite(z_near), f_reach / z_near, -1.0)
+    out = np.zeros(len(us), bool)
+    xs, ys = np.floor(us + 0.5).astype(np.int64), np.floor(vs + 0.5).astype(np.int64)
+    r_max = int(np.ceil(radius.max())) + 1
+    for dy in range(-r_max, r_max + 1):
+        for dx in range(-r_max, r_max + 1):
+            y, x = ys + dy, xs + dx
+            ok = (y >= 0) & (y < H) & (x >= 0) & (x < W)
+            y, x = np.where(ok, y, 0), np.where(ok, x, 0)
+            out |= ok & (radius[y, x] >= np.hypot(x - us, y - vs)) & (z_near[y, x] < z_limit)
+    return out
+
+
+def occluded64(b, s, points, margin, reach=REACH):
+    """-> (occluded, visible, grey) bool [n] for points [n,3] seen from camera s of track b (module docstring)"""
+    sc = scene()
+    T = sc.truth[b][s]
+    K, R, t = (np.asarray(a, np.float64) for a in (sc.K, sc.R[b, s], sc.t[b, s]))
+    P = np.asarray(points, np.float64).reshape(-1, 3)
+    C = -R.T @ t
+    e = P - C
+    length = np.linalg.norm(e, axis=1)
+    first, _ = ray_mesh(C, e / length[:, None], sc.meshes[b]["verts"], sc.meshes[b]["faces"])
+    occluded = first < length - 2 * margin
+    visible = first >= length - margin / 2
+    Xc = P @ R.T + t
+    with np.errstate(all="ignore"):
+        us = K[0, 0] * Xc[:, 0] / Xc[:, 2] + K[0, 2]
+        vs = K[1, 1] * Xc[:, 1] / Xc[:, 2] + K[1, 2]
+        inside = (Xc[:, 2] > 0) & (us >= -0.5) & (us < W - 0.5) & (vs >= -0.5) & (vs < H - 0.5)
+    near = near_silhouette(T, K[0, 0] * reach * (margin / 2), np.where(inside, us, 0.0), np.where(inside, vs, 0.0),
+                           Xc[:, 2] - 2 * margin)
+    grey = ~inside | near | ~(occluded | visible)
+    return occluded & ~grey, visible & ~grey, grey
 
 
 @functools.lru_cache(maxsize=1)
