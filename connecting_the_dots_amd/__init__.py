@@ -11,6 +11,8 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          share is in torchext._common (checks, launch plumbing) and torchext._track (posed views)
     _lib                 ctypes binding of libctd_hip.so; build: `python -m connecting_the_dots_amd.build`
     synth, renderer, hyperdepth, nets, train, sharding   the data, model and training side above torchext
+    bandsgm              band-limited semi-global matching (include/ext/ctd_hip_band_sgm.h): the band matchers' scores as a
+                         band volume of `slots` planes, and SGM aggregation within every pixel's own disparity range
     mesh                 the triangle mesh of a TSDF volume (include/ctd_hip_mesh.h) for renderer.MeshBVH, and PLY files
     meshops              mesh clean-up (include/ctd_hip_mesh_clean.h): connected components, removal of small components,
                          of faces with coincident vertices and of unreferenced vertices, compaction

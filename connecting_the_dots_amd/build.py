@@ -32,7 +32,9 @@ def sources():
 
 
 def _headers():
-    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(os.path.dirname(HEADER), "*.h"))
+    inc = os.path.dirname(HEADER)
+    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h")) + \
+        glob.glob(os.path.join(inc, "ext", "*.h"))
 
 
 def _obj(src):
