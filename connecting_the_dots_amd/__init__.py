@@ -26,6 +26,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
                          cluster's vertex at the minimum of its summed plane quadrics, duplicate faces dropped
     meshsdf              signed nearest-face queries (include/ctd_hip_mesh_sdf.h): the side by the angle-weighted pseudonormal,
                          a distance cutoff, a mesh back into a TSDF volume, the signed error of one mesh against another
+    meshreg              point-to-mesh ICP (include/ext/ctd_hip_mesh_register.h): the 6 x 6 system of a point set under K poses
+                         against a mesh, the pose update, the loop with the last round's faces as a hint, a mesh registered
+                         to a mesh through its surface samples, and the reconstruction error after alignment
     _meshargs            what the seven mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """

@@ -3,7 +3,7 @@
 // instantiate.  The selection rule, the forward-error argument that makes pruning safe, and the shape of the two
 // kernels are derived in point_mesh.hip's header comment; this file only holds the code.
 //
-// Two compile-time switches, neither of which changes a bit of d2, face or closest where it is off:
+// Three compile-time switches, none of which changes a bit of d2, face or closest where it is off:
 //   kCutoff  a face qualifies only when its d2 compares <= max_d2 (and < +inf, as always).  The tree prunes a node when
 //            its bound exceeds min(best d2, max_d2): by (2) of point_mesh.hip every face under such a node has
 //            d2 >= fl(L L) > max_d2, so none of them can qualify, and the argument for the best d2 is as before.  With
@@ -11,6 +11,20 @@
 //            already) and min(best, +inf) = best: the answer is the uncut one, bit for bit.
 //   kBranch  the branch that point_tri took for the winning face (PointTri::region) is stored as int8 in `feature`,
 //            -1 where no face qualifies.
+//   kHint    `hint` int32 [n_points] (NULL: none) names the face each point had last time (mesh_register.hip feeds a
+//            round's answer to the next).  A hint h is used when 0 <= h < n_faces and the three vertex indices of face h
+//            lie in [0, n_verts); any other value is ignored and nothing is dereferenced through it.  Before the traversal
+//            starts, point_tri is evaluated on face h, and if its d2 qualifies (< +inf, and <= max_d2 under a cutoff) the
+//            traversal starts from that face as `best` instead of nearest_none().  Nothing else changes.
+//            The result is the unhinted one bit for bit, for any hint whatever.  A hinted face is a real candidate: a
+//            face of the mesh that brute force visits too, evaluated by the same point_tri on the same vertex bits (the
+//            tree's leaves hold copies of them), and taken only if it qualifies.  The selection keeps the smallest d2 and
+//            the lowest index among equals (r.d2 == best.d2 && f < best.face), which does not depend on the order in
+//            which candidates arrive, so starting from one of them is one more visiting order.  And a node is pruned
+//            only when its bound exceeds the limit, min(best d2, max_d2): by (2) of point_mesh.hip every face under it
+//            then has d2 > best d2 strictly, so a face of equal d2 and lower index than the hinted one is never under a
+//            pruned node and is still reached.  A good hint only makes the limit tight from the first node on.
+//            The brute-force kernel takes the switch and ignores the hint: it visits every face anyway.
 #pragma once
 
 #include <cstdint>
@@ -54,7 +68,7 @@ __device__ inline void nearest_store(const Nearest& b, long i, float* __restrict
   if (kBranch) feature[i] = (int8_t)b.region;
 }
 
-template <bool kCutoff, bool kBranch>
+template <bool kCutoff, bool kBranch, bool kHint>
 __global__ __launch_bounds__(kBruteThreads) void point_mesh_brute_kernel(const float* __restrict__ points, int n_points,
                                                                          const float* __restrict__ verts, int n_verts,
                                                                          const int* __restrict__ faces, int n_faces,
@@ -111,8 +125,11 @@ __device__ __forceinline__ float prune_limit(float best_d2, float max_d2) {
   return kCutoff && max_d2 < best_d2 ? max_d2 : best_d2;
 }
 
-template <bool kCutoff, bool kBranch>
+// verts, n_verts, faces and hint are read under kHint only
+template <bool kCutoff, bool kBranch, bool kHint>
 __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const float* __restrict__ points, int n_points,
+                                                            const float* __restrict__ verts, int n_verts,
+                                                            const int* __restrict__ faces, const int* __restrict__ hint,
                                                             float max_d2, float* __restrict__ d2, int* __restrict__ face,
                                                             float* __restrict__ closest, int8_t* __restrict__ feature) {
   int* stack = lane_stack();
@@ -121,6 +138,16 @@ __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const fl
   const float p[3] = {points[i * 3], points[i * 3 + 1], points[i * 3 + 2]};
   const bool exact = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);   // otherwise: visit every face
   Nearest best = nearest_none();
+  if (kHint && hint) {
+    const int h = hint[i];
+    if (h >= 0 && h < bv.n) {                          // (bv.n is n_faces)
+      const int i0 = faces[(long)h * 3], i1 = faces[(long)h * 3 + 1], i2 = faces[(long)h * 3 + 2];
+      if (i0 >= 0 && i0 < n_verts && i1 >= 0 && i1 < n_verts && i2 >= 0 && i2 < n_verts) {
+        const PointTri r = point_tri(p, verts + (long)i0 * 3, verts + (long)i1 * 3, verts + (long)i2 * 3);
+        if (r.d2 < best.d2 && (!kCutoff || r.d2 <= max_d2)) nearest_take(best, r, h);
+      }
+    }
+  }
   int sp = 0, cur = bv.n > 0 ? 0 : -1;
   while (true) {
     if (cur < 0) {                                     // pop until a node survives the best as it is now
@@ -164,17 +191,18 @@ __global__ __launch_bounds__(64) void point_mesh_bvh_kernel(BvhView bv, const fl
 }
 
 // the launches of the two kernels behind tree_or_brute, for both entry points
-template <bool kCutoff, bool kBranch>
+template <bool kCutoff, bool kBranch, bool kHint = false>
 static int nearest_launch(const float* points, int n_points, const float* verts, int n_verts, const int* faces, int n_faces,
-                          const void* bvh, float max_d2, float* d2, int* face, float* closest, int8_t* feature, hipStream_t s) {
+                          const void* bvh, float max_d2, float* d2, int* face, float* closest, int8_t* feature, hipStream_t s,
+                          const int* hint = nullptr) {
   return tree_or_brute(
       bvh, n_faces, s,
       [&](const BvhView& bv) {
-        hipLaunchKernelGGL((point_mesh_bvh_kernel<kCutoff, kBranch>), dim3((unsigned)ceil_div(n_points, 64)), dim3(64), 0, s, bv,
-                           points, n_points, max_d2, d2, face, closest, feature);
+        hipLaunchKernelGGL((point_mesh_bvh_kernel<kCutoff, kBranch, kHint>), dim3((unsigned)ceil_div(n_points, 64)), dim3(64), 0,
+                           s, bv, points, n_points, verts, n_verts, faces, hint, max_d2, d2, face, closest, feature);
       },
       [&] {
-        hipLaunchKernelGGL((point_mesh_brute_kernel<kCutoff, kBranch>), dim3((unsigned)ceil_div(n_points, kBruteThreads)),
+        hipLaunchKernelGGL((point_mesh_brute_kernel<kCutoff, kBranch, kHint>), dim3((unsigned)ceil_div(n_points, kBruteThreads)),
                            dim3(kBruteThreads), 0, s, points, n_points, verts, n_verts, faces, n_faces, max_d2, d2, face, closest,
                            feature);
       });

@@ -17,20 +17,16 @@
 //   icp_update_kernel    -- one thread per view, f64: LDL^T of the damped 6 x 6 system, the three solves, Rodrigues, the
 //     composition with the poses, one rounding to f32.
 // No atomics, no flag that another workgroup waits on: the same bits on every run.
+// The accumulation of a row, the workgroup's reduction, icp_finish_kernel and the solve up to the Rodrigues step live in
+// ctd_icp_solve.h, which mesh_register.hip includes too; they are the code that stood here.
 #include "../../include/ctd_hip_icp.h"
 #include "ctd_common.h"
+#include "ctd_icp_solve.h"
 #include "ctd_validate.h"
 #include "ctd_view.h"
 
 namespace ctd {
 namespace {
-
-constexpr int kIcpThreads = 256;                              // threads of a workgroup of the system kernel
-constexpr int kIcpPix = 4;                                    // pixels per thread before the cross-lane step
-constexpr int kIcpChunk = kIcpThreads * kIcpPix;              // pixels per workgroup
-constexpr int kSys = 29;                                      // 21 + 6 + 1 + 1 entries of a system
-
-__device__ inline bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }   // (a NaN fails the compare)
 
 // the view that view s is aligned to, or -1: skipped (target NULL: zeros)
 __device__ inline int icp_target(const int32_t* __restrict__ target, long bv, int s, int V) {
@@ -146,21 +142,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_system_kernel(
               e = n0 * D0 + n1 * D1 + n2 * D2;
               hit = track + ga;
               const float Jf[6] = {S[1] * n2 - S[2] * n1, S[2] * n0 - S[0] * n2, S[0] * n1 - S[1] * n0, n0, n1, n2};
-              double J[6];
-#pragma unroll
-              for (int i = 0; i < 6; ++i) J[i] = (double)Jf[i];
-              const double ed = (double)e;
-              int m = 0;
-#pragma unroll
-              for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) {
-                  acc[m] = fma(J[i], J[j], acc[m]);           // the product is exact in f64: one rounding, that of the sum
-                  ++m;
-                }
-#pragma unroll
-              for (int i = 0; i < 6; ++i) acc[21 + i] = fma(J[i], ed, acc[21 + i]);
-              acc[27] = fma(ed, ed, acc[27]);
+              icp_accumulate(acc, Jf, e);
               acc[28] = acc[28] + 1.0;
             }
           }
@@ -170,35 +152,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_system_kernel(
     if (residual) residual[track + gl] = e;
     if (assoc) assoc[track + gl] = hit;
   }
-  // one reduction per workgroup: lanes, then wavefronts
-#pragma unroll
-  for (int e = 0; e < kSys; ++e) {
-    double v = acc[e];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-    acc[e] = v;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int e = 0; e < kSys; ++e) wave_sum[wave][e] = acc[e];
-  }
-  __syncthreads();
-  if (threadIdx.x < kSys) {
-    double v = wave_sum[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kIcpThreads / 64; ++w) v = v + wave_sum[w][threadIdx.x];
-    partial[(long)blockIdx.x * kSys + threadIdx.x] = v;
-  }
-}
-
-__global__ __launch_bounds__(64) void icp_finish_kernel(const double* __restrict__ partial, double* __restrict__ system,
-                                                        int chunks) {
-  if (threadIdx.x >= kSys) return;
-  const double* p = partial + (long)blockIdx.x * chunks * kSys + threadIdx.x;
-  double v = p[0];
-  for (int c = 1; c < chunks; ++c) v = v + p[(long)c * kSys];
-  system[(long)blockIdx.x * kSys + threadIdx.x] = v;
+  icp_block_reduce(acc, wave_sum, partial + (long)blockIdx.x * kSys);   // one reduction per workgroup
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -215,80 +169,13 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const double* __restrict
   const double* sys = system + bv * kSys;
   const float* Rs = R + bv * 9;
   const float* ts = t + bv * 3;
-  double A[6][6], L[6][6], D[6], g[6];
-  {
-    int m = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j) {
-        A[i][j] = sys[m];
-        A[j][i] = sys[m];
-        ++m;
-      }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) g[i] = sys[21 + i];
-  bool ok = a >= 0 && sys[28] >= min_count;                   // (a NaN count fails the compare)
-  // every column is factored, also behind a pivot that fails (ok only ever falls): fully unrolled, all in registers
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = A[j][j] + damping * A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d = d - (L[j][k] * L[j][k]) * D[k];
-    ok = ok && fabs(d) < (double)__builtin_inff() && d > min_pivot * A[j][j];      // (a NaN fails the compares)
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v = v - (L[i][k] * L[j][k]) * D[k];
-      L[i][j] = v / d;
-    }
-  }
-  if (!ok) {
+  double x[6], Rr[3][3];
+  if (!icp_solve(sys, a >= 0, min_count, min_pivot, damping, x, Rr)) {
     for (int i = 0; i < 9; ++i) R_out[bv * 9 + i] = Rs[i];
     for (int i = 0; i < 3; ++i) t_out[bv * 3 + i] = ts[i];
     ok_out[bv] = 0;
     return;
   }
-  double x[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double v = -g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v = v - L[i][k] * x[k];
-    x[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) x[i] = x[i] / D[i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double v = x[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) v = v - L[k][i] * x[k];
-    x[i] = v;
-  }
-  const double w0 = x[0], w1 = x[1], w2 = x[2];
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
-  double ca, cb;
-  if (th < 1e-4) {
-    ca = 1.0 - th2 / 6.0;
-    cb = 0.5 - th2 / 24.0;
-  } else {
-    ca = sin(th) / th;
-    cb = (1.0 - cos(th)) / th2;
-  }
-  const double w[3] = {w0, w1, w2};
-  const double Wx[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-  double Rr[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double dij = i == j ? 1.0 : 0.0;
-      Rr[i][j] = dij + ca * Wx[i][j] + cb * (w[i] * w[j] - th2 * dij);
-    }
   const float* Raf = R + (b * V + a) * 9;
   const float* taf = t + (b * V + a) * 3;
   double Ra[3][3], Rsd[3][3], ta[3], tsd[3];
