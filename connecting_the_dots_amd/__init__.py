@@ -29,6 +29,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
     meshreg              point-to-mesh ICP (include/ext/ctd_hip_mesh_register.h): the 6 x 6 system of a point set under K poses
                          against a mesh, the pose update, the loop with the last round's faces as a hint, a mesh registered
                          to a mesh through its surface samples, and the reconstruction error after alignment
+    meshrobust           robust point-to-mesh ICP (include/ext/ctd_hip_mesh_robust.h): meshreg's system with Huber or Tukey
+                         weights, matches on the rim of an open mesh rejected and a normal gate; the per-face rim table,
+                         the scale from a round's residuals, the loop, and the reconstruction error after alignment
     _meshargs            what the seven mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """

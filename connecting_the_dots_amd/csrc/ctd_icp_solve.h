@@ -1,8 +1,10 @@
 // ctd_icp_solve.h -- what the two ICPs share: depth_icp.hip (include/ctd_hip_icp.h, a view of a track against another)
-// and mesh_register.hip (include/ext/ctd_hip_mesh_register.h, a point set against a mesh).  Both build the same 29-entry
+// and mesh_register.hip / mesh_robust.hip (include/ext/ctd_hip_mesh_register.h, ctd_hip_mesh_robust.h, a point set against a
+// mesh, plain and weighted).  All build the same 29-entry
 // f64 system in the same fixed order and solve it the same way; they differ in where a residual and its Jacobian row
 // come from and in how the step is composed with a pose.  The rules are stated word for word in include/ctd_hip_icp.h.
 //   icp_accumulate   -- one row (J, e) into a thread's 28 sums (the count is the caller's: a point may have three rows).
+//   icp_accumulate_weighted -- the same row under a weight w (mesh_robust.hip): w * (x * y), two roundings, no fma.
 //   icp_block_reduce -- ONE reduction per workgroup of kIcpThreads: a butterfly over the lane distances 32 .. 1 (an add
 //     commutes, so every lane ends with the same bits), the four wavefronts ascending through LDS, 29 f64 written.
 //   icp_finish_kernel -- one wavefront per system: lane e < 29 sums entry e of the system's workgroups, ascending.
@@ -38,6 +40,27 @@ __device__ __forceinline__ void icp_accumulate(double (&acc)[kSys], const float 
 #pragma unroll
   for (int i = 0; i < 6; ++i) acc[21 + i] = fma(J[i], ed, acc[21 + i]);
   acc[27] = fma(ed, ed, acc[27]);
+}
+
+// the same row under a weight (mesh_robust.hip): every term is w * (x * y), the inner product exact, the multiplication
+// by w the one rounding before that of the sum; deliberately no fma, which would round once.  With w == 1 the sums are
+// icp_accumulate's bit for bit.
+__device__ __forceinline__ void icp_accumulate_weighted(double (&acc)[kSys], const float (&Jf)[6], float e, float w) {
+  double J[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) J[i] = (double)Jf[i];
+  const double ed = (double)e, wd = (double)w;
+  int m = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = i; j < 6; ++j) {
+      acc[m] = acc[m] + wd * (J[i] * J[j]);
+      ++m;
+    }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + wd * (J[i] * ed);
+  acc[27] = acc[27] + wd * (ed * ed);
 }
 
 // lanes, then wavefronts; out = the workgroup's 29 words.  Every thread of the workgroup calls it.

@@ -9,8 +9,10 @@ the surface and not a rigid offset between the two.
 
 A pose (R, t) moves a point p to S = R p + t.  What this does not do: no global registration (it converges from a few
 tens of degrees and a fraction of the object's size at best; pass several starts as R [K,3,3], t [K,3] and take
-info["best"]), no scale, no robust weights, and no rejection of matches on boundary edges: a point set that overhangs an
-open mesh pulls towards its rim, and `max_dist` is the remedy.
+info["best"]) and no scale.  No robust weights and no rejection of matches on boundary edges here either: a point set
+that overhangs an open mesh pulls towards its rim, and outliers pull as hard as their distance.  `max_dist` is the blunt
+remedy; `meshrobust` (include/ext/ctd_hip_mesh_robust.h) has Huber and Tukey weights, rim rejection and a normal gate
+on the same system.
 
 The header's prototypes are bound here, onto the library handle of `_lib.lib()` at first use; this table is not one of
 `_lib.TABLES`.  No fallback to torch: a missing kernel is an error.  Nothing is differentiable.

@@ -10,8 +10,9 @@
  *
  * What it does not do.  No global registration: it converges from the errors a local method converges from (degrees
  * and a fraction of the object's size), and K starts cost one launch so that a caller can try several.  No scale.  No
- * robust weights.  No rejection of matches on boundary edges: a point set that overhangs an open mesh pulls towards its
- * rim, and max_d2 is the remedy.
+ * robust weights and no rejection of matches on boundary edges in these calls: a point set that overhangs an open mesh
+ * pulls towards its rim, and max_d2 is the blunt remedy.  ctd_hip_mesh_robust.h, next to this header, has the weighted
+ * and gated system (Huber and Tukey weights, rim rejection, a normal gate); its update is the one below.
  *
  * Common to the calls.  All f32 arithmetic is in the written association and uncontracted.  The cross product u x w is
  * (u1*w2 - u2*w1, u2*w0 - u0*w2, u0*w1 - u1*w0), each component two f32 products and one f32 subtraction, as in
