@@ -32,6 +32,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
     meshrobust           robust point-to-mesh ICP (include/ext/ctd_hip_mesh_robust.h): meshreg's system with Huber or Tukey
                          weights, matches on the rim of an open mesh rejected and a normal gate; the per-face rim table,
                          the scale from a round's residuals, the loop, and the reconstruction error after alignment
+    meshglobal           global point-to-mesh registration (include/ext/ctd_hip_mesh_global.h): a grid of rotations x offsets
+                         scored exactly against a volume of uint8 distance levels, the best few refined by meshreg's or
+                         meshrobust's loop and ranked by the point metric; registration from any starting orientation
     _meshargs            what the seven mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """

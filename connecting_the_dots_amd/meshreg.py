@@ -9,7 +9,8 @@ the surface and not a rigid offset between the two.
 
 A pose (R, t) moves a point p to S = R p + t.  What this does not do: no global registration (it converges from a few
 tens of degrees and a fraction of the object's size at best; pass several starts as R [K,3,3], t [K,3] and take
-info["best"]) and no scale.  No robust weights and no rejection of matches on boundary edges here either: a point set
+info["best"]; `meshglobal.global_mesh_icp` finds such starts from any orientation and refines them with this loop) and
+no scale.  No robust weights and no rejection of matches on boundary edges here either: a point set
 that overhangs an open mesh pulls towards its rim, and outliers pull as hard as their distance.  `max_dist` is the blunt
 remedy; `meshrobust` (include/ext/ctd_hip_mesh_robust.h) has Huber and Tukey weights, rim rejection and a normal gate
 on the same system.

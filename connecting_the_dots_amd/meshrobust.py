@@ -10,7 +10,8 @@ fragments (outliers), registered against a truth mesh that is open (walls, table
     rim = meshrobust.face_rim(truth_faces, truth_verts.shape[0])              # once per mesh; pass it as rim=
 
 A pose (R, t) moves a point p to S = R p + t, and the update is `meshreg.mesh_icp_update`, unchanged.  What this does
-not do: no global registration and no scale, as `meshreg`.
+not do: no global registration (`meshglobal.global_mesh_icp(..., robust=dict(...))` finds the starts and runs this
+loop on them) and no scale, as `meshreg`.
 
 The header's prototypes are bound here, onto the library handle of `_lib.lib()` at first use; this table is not one of
 `_lib.TABLES`.  No fallback to torch: a missing kernel is an error.  Nothing is differentiable.

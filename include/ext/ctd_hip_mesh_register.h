@@ -9,7 +9,8 @@
  * and `stream` mean what they mean there.  No buffer a call writes may overlap another buffer of the call.
  *
  * What it does not do.  No global registration: it converges from the errors a local method converges from (degrees
- * and a fraction of the object's size), and K starts cost one launch so that a caller can try several.  No scale.  No
+ * and a fraction of the object's size), and K starts cost one launch so that a caller can try several;
+ * ctd_hip_mesh_global.h, next to this header, scores a grid of poses and so finds the starts to try.  No scale.  No
  * robust weights and no rejection of matches on boundary edges in these calls: a point set that overhangs an open mesh
  * pulls towards its rim, and max_d2 is the blunt remedy.  ctd_hip_mesh_robust.h, next to this header, has the weighted
  * and gated system (Huber and Tukey weights, rim rejection, a normal gate); its update is the one below.

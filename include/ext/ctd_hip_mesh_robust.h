@@ -8,7 +8,8 @@
  * unchanged): include what you call.  The status codes are those of ctd_hip.h; pointers are device pointers, `device`
  * and `stream` mean what they mean there.  No buffer a call writes may overlap another buffer of the call.
  *
- * What it does not do.  No global registration and no scale, as ctd_hip_mesh_register.h.  It does not estimate the
+ * What it does not do.  No global registration (ctd_hip_mesh_global.h finds the starts) and no scale, as
+ * ctd_hip_mesh_register.h.  It does not estimate the
  * robust scale: that is a median, which the caller computes between rounds (meshrobust.robust_scale) and hands over
  * on the device.
  *
