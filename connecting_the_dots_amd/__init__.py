@@ -35,6 +35,9 @@ hand-written HIP kernels (csrc/) behind the C ABI of include/ctd_hip.h.
     meshglobal           global point-to-mesh registration (include/ext/ctd_hip_mesh_global.h): a grid of rotations x offsets
                          scored exactly against a volume of uint8 distance levels, the best few refined by meshreg's or
                          meshrobust's loop and ranked by the point metric; registration from any starting orientation
+    pointcloud           bare point sets (include/ext/ctd_hip_point_cloud.h): exact k-nearest-neighbours over a sorted grid of
+                         cells (PointGrid, knn), the statistical outlier mask, covariance normals and the voxel-mean
+                         down-sample that rest on it; for fused points before they meet a mesh
     _meshargs            what the seven mesh modules and renderer share above the C calls: argument checks, the choice of
                          a tree for a query, the steps of the *_tsdf_mesh functions
 """

@@ -13,6 +13,8 @@ truth mesh, or two tracks of one object: an arbitrary rigid motion apart.
     levels = meshglobal.distance_levels(truth_verts, truth_faces, origin, voxel, dims, trunc=6 * voxel)
     score = meshglobal.pose_scores(points[:2048], R_grid, base, offsets, levels, origin, voxel)      # int64 [M,T]
     Rk, tk, sk, mk = meshglobal.best_starts(score, R_grid, base, offsets, K=8)
+    # points[:2048] of fused points (in `src` order) is one corner of the first view; an even subset of any point set is
+    # pointcloud.voxel_downsample(points, cell).points, one mean point per occupied cell
 
 A pose (R, t) moves a point p to S = R p + t.  What this does not do: no scale and no reflection, and nothing is
 differentiable.  The search is exhaustive over a grid, not guided by features: a grid that is too coarse for the object
